@@ -19,6 +19,13 @@ Proofs (L2 scale and zelana_batch) and the NTT run as replicas at N > 1: every
 rank proves its own batches, as the forge swarm's chunk-per-worker model
 (forge/crates/prover-coordinator/src/dispatcher.rs:134,290).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline
+needs and no more: inputs and the fixed-base table, W warm-up steps, the N
+timed steps, the result line (and, with --dump-outputs DIR, the last timed
+step's result as DIR/msm_g1_result.npy).  --full adds every other measurement
+and check described here and below: the plain-Pippenger pass, the stage and
+roofline passes, config 5, G2, NTT, the proof legs and the CPU baseline.
+
 Inputs are synthetic (generated directly in HBM by libzkmi: P_i = k_i * G,
 uniform scalars) and resident before the timed region.  The CPU baseline is the
 oracle/ restatement of arkworks run on this box's host cores (every core the
@@ -49,6 +56,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log-n", type=int, default=20, help="points per GPU = 2^log_n")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side measurement and check (plain Pippenger, stage and "
+                         "roofline passes, 2^26, G2, NTT, proofs, CPU baseline); the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's result to DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-table", action="store_true", help="headline without the fixed-base table")
     ap.add_argument("--inputs", choices=("stdrng", "splitmix"), default="stdrng",
@@ -88,7 +100,15 @@ def parse():
                     help="independent scalar vectors the timed MSM loops alternate over")
     ap.add_argument("--lanes", type=int, default=2,
                     help="MSM lanes (streams with private scratch) = MSMs kept in flight in the timed loops")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        for leg in SIDE_LEGS:
+            setattr(args, "no_" + leg, True)
+    return args
+
+
+# the side measurements of a --full run (each has its --no-* option)
+SIDE_LEGS = ("plain", "big", "window_ab", "g2", "ntt", "l2", "zbatch", "cpu_baseline")
 
 
 R_FR = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -239,32 +259,39 @@ def main():
     run(2 * lanes)
     sync_all()
     last, elapsed = timed(args.steps, args.warmup, prof=args.timers_in_timed_region)
-    if not args.timers_in_timed_region:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"msm_g1_result": last})
+    if args.full and not args.timers_in_timed_region:
         _, prof_elapsed = timed(args.steps, 0, prof=True)
-    # each set's table-MSM result, untimed, through the same (at N > 1
-    # sharded, collective) submit: set 0's is what the CPU leg checks
-    set_results = [finish(submit(bases, sc, n)) for sc in scalar_sets]
-    result = set_results[0]
-    if not np.array_equal(last, set_results[last_set(args.steps)]):
-        sys.exit("bench.py: the timed loop's last MSM differs from the same MSM run alone")
-    if plain is not None:
-        plain["same_result"] = bool(np.array_equal(pres, set_results[last_set(max(1, args.steps // 2))]))
+    result = None
+    if args.full:
+        # each set's table-MSM result, untimed, through the same (at N > 1
+        # sharded, collective) submit: set 0's is what the CPU leg checks
+        set_results = [finish(submit(bases, sc, n)) for sc in scalar_sets]
+        result = set_results[0]
+        if not np.array_equal(last, set_results[last_set(args.steps)]):
+            sys.exit("bench.py: the timed loop's last MSM differs from the same MSM run alone")
+        if plain is not None:
+            plain["same_result"] = bool(np.array_equal(pres, set_results[last_set(max(1, args.steps // 2))]))
 
     kernel = "msm_acc0_g1"
     breakdown = stages(args.steps)
     ovl_tot, ovl_cnt = ctx.profile_get(kernel)
-    # Roofline pass: the dominant kernel timed in isolation (one lane, each MSM
-    # finished before the next), HIP events on the lane stream it runs on.  In
-    # the timed region several lanes overlap, which stretches every kernel's span.
-    rf_launches = 5
-    ctx.set_lanes(1)
-    ctx.profile(True)
-    ctx.profile_reset()
-    for _ in range(rf_launches):
-        ctx.msm(bases, scalars)
-    ktot, kcnt = ctx.profile_get(kernel)
-    ctx.profile(False)
-    ctx.set_lanes(lanes)
+    # Roofline pass (--full): the dominant kernel timed in isolation (one lane,
+    # each MSM finished before the next), HIP events on the lane stream it runs
+    # on.  In the timed region several lanes overlap, which stretches every
+    # kernel's span.
+    rf_launches = 5 if args.full else 0
+    ktot, kcnt = 0.0, 0
+    if args.full:
+        ctx.set_lanes(1)
+        ctx.profile(True)
+        ctx.profile_reset()
+        for _ in range(rf_launches):
+            ctx.msm(bases, scalars)
+        ktot, kcnt = ctx.profile_get(kernel)
+        ctx.profile(False)
+        ctx.set_lanes(lanes)
     kavg_s = ktot / max(kcnt, 1) / 1e3
     achieved = MSM_BYTES_PER_PAIR * n / kavg_s / 1e9 if kcnt else None
     # acc0_g1 launches before the roofline pass (for tools/rocpd_summary.py)
@@ -376,6 +403,7 @@ def main():
                             + " all-gather of partials") if world > 1 else "single GPU",
             "field": "BN254 Fq, 9x29-bit limbs, Montgomery R=2^261",
             "env": env_knobs,
+            "full": args.full,
         },
         "roofline": {
             "bound": "hbm",
@@ -385,8 +413,8 @@ def main():
             "unit": "GB/s",
             "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None,
             "traffic": traffic,
-            "kernel_avg_ms": round(kavg_s * 1e3, 4),
-            "kernel_launches": {"first": rf_first, "count": rf_launches},
+            "kernel_avg_ms": round(kavg_s * 1e3, 4) if kcnt else None,
+            "kernel_launches": {"first": rf_first, "count": rf_launches} if args.full else None,
             "kernel_avg_ms_in_timed_region": round(ovl_tot / max(ovl_cnt, 1), 4),
             "algorithmic_bytes_per_launch": MSM_BYTES_PER_PAIR * n,
             "note": "MSM is VALU-bound (256-bit modular multiplies), not HBM-bound; frac is vs HBM peak as BASELINE.md "
@@ -405,6 +433,17 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one
+    <name>.npy per array.  Field elements are uint64 limbs, which float64
+    cannot hold exactly, so each array is written as its little-endian 32-bit
+    words in float64 (an MSM result: 8 limbs -> 16 words, x then y)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        words = np.ascontiguousarray(a, dtype="<u8").view("<u4")
+        np.save(os.path.join(out_dir, name + ".npy"), words.astype(np.float64))
 
 
 def pipelined(submit, finish, k, depth):

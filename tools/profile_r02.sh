@@ -8,10 +8,10 @@ TAG=${1:-r02}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-    python3 bench.py > $OUT/bench_rocprof.json 2> $OUT/bench_rocprof.err
-SHORT="--no-plain --no-l2 --no-zbatch --no-big --no-cpu-baseline --steps 3 --warmup 1"
+    python3 bench.py --full > $OUT/bench_rocprof.json 2> $OUT/bench_rocprof.err
+SHORT="--full --no-plain --no-l2 --no-zbatch --no-big --no-cpu-baseline --steps 3 --warmup 1"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o run -- \
     python3 bench.py $SHORT > $OUT/pmc_fetch.json 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o run -- \

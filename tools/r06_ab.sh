@@ -14,7 +14,7 @@ done
 if [ -n "$LEGS" ]; then
   for rep in 1 2; do
     for v in base cur; do
-      ZKMI_LIB=zelana_amd/_ab/libzkmi_$v.so timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-plain --no-big \
+      ZKMI_LIB=zelana_amd/_ab/libzkmi_$v.so timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-plain --no-big \
         --no-window-ab --no-g2 --no-ntt --no-cpu-baseline $LEGS > $OUT/legs_${v}_$rep.json 2> $OUT/legs_${v}_$rep.err || exit 1
       python3 - $OUT/legs_${v}_$rep.json $v >> $OUT/ab.log <<'PY'
 import json, sys

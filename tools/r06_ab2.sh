@@ -16,7 +16,7 @@ for rep in 1 2; do
     ZKMI_LIB=zelana_amd/_ab/libzkmi_$v.so timeout -k 10 200 python3 tools/l2_loop.py 22 10 >> $OUT/ab.log 2>&1 || exit 1
     ZKMI_LIB=zelana_amd/_ab/libzkmi_$v.so TWO=1 timeout -k 10 200 python3 tools/l2_loop.py 22 10 >> $OUT/ab.log 2>&1 || exit 1
     if [ -n "$LEGS" ]; then
-      ZKMI_LIB=zelana_amd/_ab/libzkmi_$v.so timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-plain --no-big \
+      ZKMI_LIB=zelana_amd/_ab/libzkmi_$v.so timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-plain --no-big \
         --no-window-ab --no-g2 --no-ntt --no-cpu-baseline --no-l2 > $OUT/legs_${v}_$rep.json 2> $OUT/legs_${v}_$rep.err || exit 1
       python3 - $OUT/legs_${v}_$rep.json $v >> $OUT/ab.log <<'PY'
 import json, sys
