@@ -141,6 +141,22 @@ int zkmi_msm_wait(zkmi_msm_job* job, uint64_t* out_affine);
 int zkmi_msm_submit_shared(zkmi_ctx* ctx, const zkmi_bases* const* bs, int k, size_t offset, const void* d_scalars,
                            size_t n, zkmi_msm_job** jobs);
 int zkmi_msm_set_window(zkmi_ctx* ctx, int c);
+/* nb MSMs over ONE base set and range: vector i = n scalars at d_scalars +
+ * i * stride bytes (stride >= n * 32, a multiple of 32).  The vectors are
+ * split into groups (zkmi_ctx_set_batch_group); a group runs as one launch
+ * sequence whose sort keys carry the batch index as an outer window, so the
+ * short dependent kernels of a small MSM carry a group's work.  Results equal
+ * nb zkmi_msm_submit calls.  One job; finish it with zkmi_msm_batch_wait
+ * (zkmi_msm_wait on it, zkmi_msm_batch_wait on a single job, or another nb
+ * return ZKMI_EINVAL and leave the job valid).  nb = 0 and n = 0 are valid.
+ * Batch jobs take no communicator.  No counterpart in the reference. */
+int zkmi_msm_batch_submit(zkmi_ctx* ctx, const zkmi_bases* b, size_t offset, const void* d_scalars, size_t n,
+                          size_t nb, size_t stride, zkmi_msm_job** job);
+/* out = nb canonical affine points (nb x 8 or nb x 16 u64) */
+int zkmi_msm_batch_wait(zkmi_msm_job* job, uint64_t* out, size_t nb);
+/* proofs / MSMs per batched launch sequence: 0 = automatic (by size), 1..64 */
+int zkmi_ctx_set_batch_group(zkmi_ctx* ctx, int g);
+int zkmi_ctx_get_batch_group(const zkmi_ctx* ctx);
 /* Number of MSM lanes (streams with their own scratch) used round-robin by
  * consecutive submissions so their latency-bound tails overlap; 1..8, at most
  * 2 while a communicator exists on the context (stream budget, below). */
@@ -232,6 +248,11 @@ int zkmi_msm_window_sharded_submit(zkmi_comm* comm, const zkmi_bases* bases, siz
  * n^-1 (and g^-i when coset=1).  log_n <= 28. */
 int zkmi_ntt(zkmi_ctx* ctx, uint64_t* data, uint32_t log_n, int inverse, int coset);
 int zkmi_ntt_device(zkmi_ctx* ctx, void* d_data, uint32_t log_n, int inverse, int coset);
+/* nb transforms in one launch sequence: vector i at d_data + i * stride bytes
+ * (stride >= 2^log_n * 32, a multiple of 32; nb <= 65535).  Bytes between two
+ * vectors are not written. */
+int zkmi_ntt_batch_device(zkmi_ctx* ctx, void* d_data, uint32_t log_n, size_t nb, size_t stride, int inverse,
+                          int coset);
 
 /* ------------------------------------------------------------- Groth16 */
 /* R1CS in CSR form; variable 0 = One, instance i -> i, witness j ->
@@ -290,6 +311,24 @@ typedef struct zkmi_proof_job zkmi_proof_job;
 int zkmi_groth16_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_dev* cs, const void* d_z,
                               const uint64_t r[4], const uint64_t s[4], zkmi_proof_job** job);
 int zkmi_groth16_prove_wait(zkmi_proof_job* job, uint64_t a_out[8], uint64_t b_out[16], uint64_t c_out[8]);
+/* nb proofs of same-shape witnesses under one key: assignment i at d_z + i *
+ * z_stride bytes (the layout zkmi_wprog_run_many writes; z_stride >= n_vars *
+ * 32, a multiple of 32), blinding scalars r[4 i ..], s[4 i ..].  Domains up to
+ * 2^16: groups of proofs (zkmi_ctx_set_batch_group) run as ONE launch
+ * sequence each -- a batched witness map and batched MSMs -- instead of ~130
+ * launches per proof; larger domains run the single-proof schedule with two
+ * proofs in flight.  Proofs equal zkmi_groth16_prove_resident's, byte for
+ * byte.  d_z stays unchanged until wait returns; jobs of a context are
+ * finished in submission order (single and batched alike).  The reference
+ * proves such a stream one Groth16::prove at a time (prover.rs:408). */
+int zkmi_groth16_prove_many_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_dev* cs, const void* d_z,
+                                   size_t nb, size_t z_stride, const uint64_t* r, const uint64_t* s,
+                                   zkmi_proof_job** job);
+/* a_out nb x 8, b_out nb x 16, c_out nb x 8; nb must equal the job's */
+int zkmi_groth16_prove_many_wait(zkmi_proof_job* job, size_t nb, uint64_t* a_out, uint64_t* b_out, uint64_t* c_out);
+int zkmi_groth16_prove_many(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_dev* cs, const void* d_z, size_t nb,
+                            size_t z_stride, const uint64_t* r, const uint64_t* s, uint64_t* a_out, uint64_t* b_out,
+                            uint64_t* c_out);
 /* Benchmark helper: a random proving key of domain 2^log_n with the given
  * instance/witness counts, generated in HBM.  Proofs made with it do not
  * verify; the proving work is identical to a real key of that shape. */

@@ -75,6 +75,10 @@ SIGNATURES = [
     ("zkmi_msm_submit", ctypes.c_int, [vp, vp, sz, vp, sz, ctypes.POINTER(vp)]),
     ("zkmi_msm_wait", ctypes.c_int, [vp, u64p]),
     ("zkmi_msm_set_window", ctypes.c_int, [vp, ctypes.c_int]),
+    ("zkmi_msm_batch_submit", ctypes.c_int, [vp, vp, sz, vp, sz, sz, sz, ctypes.POINTER(vp)]),
+    ("zkmi_msm_batch_wait", ctypes.c_int, [vp, u64p, sz]),
+    ("zkmi_ctx_set_batch_group", ctypes.c_int, [vp, ctypes.c_int]),
+    ("zkmi_ctx_get_batch_group", ctypes.c_int, [vp]),
     ("zkmi_msm_set_lanes", ctypes.c_int, [vp, ctypes.c_int]),
     ("zkmi_msm_get_lanes", ctypes.c_int, [vp]),
     ("zkmi_ctx_stream_count", ctypes.c_int, [vp]),
@@ -92,6 +96,7 @@ SIGNATURES = [
     ("zkmi_g2_add", ctypes.c_int, [u64p, u64p, u64p]),
     ("zkmi_ntt", ctypes.c_int, [vp, u64p, ctypes.c_uint32, ctypes.c_int, ctypes.c_int]),
     ("zkmi_ntt_device", ctypes.c_int, [vp, vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_int]),
+    ("zkmi_ntt_batch_device", ctypes.c_int, [vp, vp, ctypes.c_uint32, sz, sz, ctypes.c_int, ctypes.c_int]),
     ("zkmi_witness_map", ctypes.c_int, [vp, ctypes.POINTER(R1CSStruct), u64p, u64p]),
     ("zkmi_pk_load", ctypes.c_int, [vp, u8p, sz, ctypes.c_int, ctypes.POINTER(vp)]),
     ("zkmi_pk_destroy", None, [vp]),
@@ -105,6 +110,9 @@ SIGNATURES = [
     ("zkmi_groth16_prove_resident", ctypes.c_int, [vp, vp, vp, vp, u64p, u64p, u64p, u64p, u64p]),
     ("zkmi_groth16_prove_submit", ctypes.c_int, [vp, vp, vp, vp, u64p, u64p, ctypes.POINTER(vp)]),
     ("zkmi_groth16_prove_wait", ctypes.c_int, [vp, u64p, u64p, u64p]),
+    ("zkmi_groth16_prove_many_submit", ctypes.c_int, [vp, vp, vp, vp, sz, sz, u64p, u64p, ctypes.POINTER(vp)]),
+    ("zkmi_groth16_prove_many_wait", ctypes.c_int, [vp, sz, u64p, u64p, u64p]),
+    ("zkmi_groth16_prove_many", ctypes.c_int, [vp, vp, vp, vp, sz, sz, u64p, u64p, u64p, u64p, u64p]),
     ("zkmi_pk_synthetic", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint32, sz, sz, ctypes.POINTER(vp)]),
     ("zkmi_groth16_setup", ctypes.c_int, [vp, vp, u64p, u64p, u64p, ctypes.POINTER(vp)]),
     ("zkmi_pk_serialize", ctypes.c_int, [vp, u8p, sz, ctypes.POINTER(sz)]),

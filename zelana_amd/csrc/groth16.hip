@@ -55,6 +55,8 @@ int ntt_raw(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit);
 int ntt_raw_epi(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, int epi, const uint32_t* lo,
                 const uint32_t* hi);
 int ntt_bitrev(zkmi_ctx* ctx, uint32_t* d, uint32_t logn);
+int ntt_raw_epi_n(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, int epi, const uint32_t* lo,
+                  const uint32_t* hi, unsigned nb, size_t vstr);
 
 // ------------------------------------------------------------ decoding
 __constant__ uint32_t FQ_MOD32[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
@@ -234,9 +236,14 @@ __global__ void __launch_bounds__(256) k_permute_rev(const uint32_t* __restrict_
 
 // ------------------------------------------------------------ witness map
 // z (canonical) -> Montgomery copy for the mat-vec
-__global__ void __launch_bounds__(256) k_to_mont_fr(const uint32_t* __restrict__ z, size_t n, uint32_t* __restrict__ zm) {
+// (batched witness map: grid row blockIdx.y is the assignment, zstr words
+// after the one before; its copy is packed, n elements per row)
+__global__ void __launch_bounds__(256) k_to_mont_fr(const uint32_t* __restrict__ z, size_t n, uint32_t* __restrict__ zm,
+                                                    size_t zstr = 0) {
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
+  z += (size_t)blockIdx.y * zstr;
+  zm += (size_t)blockIdx.y * n * 8;
   st_fe(zm + i * 8, to_mont<FrP>(ld_fe(z + i * 8)));
 }
 // rows i < m: out[i] = sum_k val_k * z[col_k]  (val canonical, z Montgomery ->
@@ -286,13 +293,22 @@ __device__ __forceinline__ Fe mv_term(uint64_t k, const uint64_t* __restrict__ c
     return mul<FrP>(ld_fe(val + k * 8), ld_fe(zm + col[k] * 8));
   }
 }
-template <bool DICT, class RP>
+// BAT (batched witness map): blockIdx.y is the assignment: z at zc + y * zstr
+// words (its Montgomery copy at zm + y * zmstr), the output vector at out + y
+// * n elements; the matrices are shared.
+template <bool DICT, class RP, bool BAT = false>
 __global__ void __launch_bounds__(256) k_matvec(const RP* __restrict__ rowptr, const uint64_t* __restrict__ col,
                                                 const uint32_t* __restrict__ val, const uint2* __restrict__ cv,
                                                 const uint32_t* __restrict__ coef, const uint32_t* __restrict__ zm,
                                                 const uint32_t* __restrict__ zc, size_t m, size_t l, size_t n,
                                                 int is_a, const uint32_t* __restrict__ lrow, uint32_t nlong, int g,
-                                                uint32_t nsb, uint32_t* __restrict__ out) {
+                                                uint32_t nsb, uint32_t* __restrict__ out, size_t zstr = 0,
+                                                size_t zmstr = 0) {
+  if (BAT) {
+    zc += (size_t)blockIdx.y * zstr;
+    if (!DICT) zm += (size_t)blockIdx.y * zmstr;
+    out += (size_t)blockIdx.y * n * 8;
+  }
   if (blockIdx.x < nsb) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -675,6 +691,54 @@ static int witness_map_dev(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z
   return 0;
 }
 
+// The witness map of nb assignments (z_i at d_z + i * zstr words) in one launch
+// sequence: d_v holds 3 nb vectors of n elements -- a_0..a_{nb-1}, then the
+// b's, then the c's -- so each NTT direction is one batched launch sequence
+// over all 3 nb of them; h_i (bit-reversed layout, as witness_map_dev) ends up
+// in a_i = d_v + i * n elements.  ws: nb (3 n [+ nv]) x 32 B.
+static int witness_map_many(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, size_t zstr, unsigned nb,
+                            uint32_t logn, uint32_t* d_v) {
+  hipStream_t st = ctx->stream;
+  size_t m = dr.m, l = dr.l, nv = l + dr.w;
+  size_t n = (size_t)1 << logn;
+  DomainCache dc;
+  ZK_TRY(domain_cache(ctx, logn, &dc));
+  const bool legacy = !dr.dict[0] || !dr.dict[1] || !dr.dict[2];
+  uint32_t* zm = nullptr;
+  if (legacy) ZK_TRY(ctx->ws.get("wm_zmb", (size_t)nb * nv * 32, (void**)&zm));
+  const size_t vw = n * 8;  // words per vector
+  uint32_t *a = d_v, *b = d_v + (size_t)nb * vw, *c = d_v + 2 * (size_t)nb * vw;
+  unsigned gn = (unsigned)((n + 255) / 256);
+  {
+    ScopedKernelTimer tm(ctx, "g16_matvec");
+    if (legacy) k_to_mont_fr<<<dim3((unsigned)((nv + 255) / 256), nb), 256, 0, st>>>(d_z, nv, zm, zstr);
+    uint32_t* outs[3] = {a, b, c};
+    for (int t = 0; t < 3; t++) {
+      const unsigned gl = (unsigned)(((size_t)dr.nlong[t] * dr.glong[t] + 255) / 256);
+      if (dr.dict[t])
+        k_matvec<true, uint32_t, true><<<dim3(gn + gl, nb), 256, 0, st>>>(
+            dr.rp32[t], nullptr, nullptr, dr.cv[t], dr.coef[t], zm, d_z, m, l, n, t == 0, dr.lrow[t], dr.nlong[t],
+            dr.glong[t], gn, outs[t], zstr, nv * 8);
+      else
+        k_matvec<false, uint64_t, true><<<dim3(gn + gl, nb), 256, 0, st>>>(
+            dr.rp[t], dr.col[t], dr.val[t], nullptr, nullptr, zm, d_z, m, l, n, t == 0, dr.lrow[t], dr.nlong[t],
+            dr.glong[t], gn, outs[t], zstr, nv * 8);
+    }
+    ZK_HIP(hipGetLastError());
+  }
+  // as witness_map_dev, over all 3 nb vectors at once
+  ZK_TRY(ntt_raw_epi_n(ctx, d_v, logn, 1, false, 2, dc.lo_g, dc.hi_g, 3 * nb, vw));
+  ZK_TRY(ntt_raw_epi_n(ctx, d_v, logn, 0, true, 0, nullptr, nullptr, 3 * nb, vw));
+  {
+    ScopedKernelTimer tm(ctx, "g16_qap");
+    const size_t tot = (size_t)nb * n;  // element-wise over the nb a's, b's and c's
+    k_qap_combine<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(a, b, c, tot, dc.consts + 8);
+  }
+  ZK_TRY(ntt_raw_epi_n(ctx, a, logn, 1, false, 2, dc.lo_gi, dc.hi_gi, nb, vw));
+  ZK_HIP(hipGetLastError());
+  return 0;
+}
+
 static int check_cs(const zkmi_r1cs* cs) {
   if (!cs || cs->num_instance < 1) {
     set_error("r1cs: need at least the One variable (num_instance >= 1)");
@@ -873,10 +937,13 @@ int pk_load(zkmi_ctx* ctx, const uint8_t* bytes, size_t len, int compressed, zkm
 }
 
 // ------------------------------------------------------------ B-query compaction
+// (batched: grid row blockIdx.y is the assignment, zstr words apart; its n gathered scalars are packed)
 __global__ void __launch_bounds__(256) k_gather_scalars(const uint32_t* __restrict__ z, const uint32_t* __restrict__ idx,
-                                                        size_t n, uint32_t* __restrict__ out) {
+                                                        size_t n, uint32_t* __restrict__ out, size_t zstr = 0) {
   size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
+  z += (size_t)blockIdx.y * zstr;
+  out += (size_t)blockIdx.y * n * 8;
   const uint4* s = reinterpret_cast<const uint4*>(z + (size_t)idx[k] * 8);
   uint4* d = reinterpret_cast<uint4*>(out + k * 8);
   d[0] = s[0];
@@ -980,6 +1047,22 @@ struct zkmi_proof_job {
   zkmi_msm_job* jobs[5];  // h, l, a, b_g1, b_g2
   uint64_t r[4], s[4];
   zk::G16Asm asm_st;  // the staged assembly (msm_host.cpp)
+  // Batched proving (zkmi_groth16_prove_many_submit).  The job handed to the
+  // caller (many) owns its proofs' parts in order.  A part is either a group
+  // of gnb proofs in one launch sequence (jobs[] are then batch MSM jobs of
+  // gnb vectors each; rs / ss / asms one entry per proof), or, above the small
+  // schedule, a single proof's ordinary job (gnb = 0).
+  bool many = false;
+  size_t nb = 0, gnb = 0;
+  std::vector<zkmi_proof_job*> parts;
+  std::vector<uint64_t> rs, ss;  // nb x 4 (the many job keeps every proof's)
+  std::vector<zk::G16Asm> asms;
+  // above the small schedule: proofs are submitted as the earlier ones are
+  // waited for (two in flight), so the inputs are kept
+  zkmi_ctx* ctx = nullptr;
+  const zkmi_r1cs_dev* dr = nullptr;
+  const uint32_t* dz = nullptr;
+  size_t zstr = 0, next = 0;
 };
 
 namespace zk {
@@ -1162,6 +1245,186 @@ int groth16_prove_resident(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, 
   zkmi_proof_job* pj = nullptr;
   ZK_TRY(groth16_prove_submit(ctx, pk, dr, dz, r, s, &pj));
   return groth16_prove_wait(pj, a_out, b_out, c_out);
+}
+
+// ------------------------------------------------------------ batched prove
+// nb proofs of same-shape witnesses under one key.  Small schedule (domains <=
+// SMALL_PROOF_MAX): the proofs are split into groups of at most G; a group is
+// ONE launch sequence -- prove_submit_small's lane order and fork events, with
+// the witness map and every MSM in their batched forms -- so its ~130 launches
+// carry gnb proofs' work.  Groups pipeline like proofs in flight.  G:
+// zkmi_ctx_set_batch_group, or automatic: 16 below a 2^13 domain, 8 from there
+// to SMALL_PROOF_MAX (measured, DESIGN.md section 2.5: on synthetic keys 16
+// beats 8 by 5-11% up to 2^12 and by 4-13% above; on the product key, 2^13, 8
+// beats 16 by 8% at 64 proofs and 26% at 16, where two groups of 8 overlap on
+// the lanes and one group of 16 cannot).  A group's witness-map workspace is
+// G (3 n + nv) x 32 B: <= 84 MB at 2^16 with nv <= 2 n.
+// Above SMALL_PROOF_MAX one proof fills the part: the existing schedule runs
+// with two proofs in flight (correct, not batched).
+static int prove_group_size(const zkmi_ctx* ctx, size_t n) {
+  if (ctx->batch_group > 0) return ctx->batch_group;
+  return n < ((size_t)1 << 13) ? 16 : 8;
+}
+
+static void proof_job_free(zkmi_proof_job* pj) {
+  if (!pj) return;
+  for (zkmi_proof_job* part : pj->parts) proof_job_free(part);
+  for (auto*& j : pj->jobs)
+    if (j) msm_job_free(j), j = nullptr;
+  delete pj;
+}
+
+// one group: batch i's assignment at dz + i * zstr words
+static int prove_group_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, const uint32_t* dz, size_t zstr,
+                              size_t gnb, uint32_t logn, zkmi_proof_job* pj) {
+  const size_t l = dr.l, w = dr.w, nv = l + w, n = pk->n;
+  const int nl = std::max(1, ctx->msm_lanes);
+  const size_t zsb = zstr * 4;  // bytes
+  zkmi_msm_job** jobs = pj->jobs;
+  if (!ctx->prove_fork) ZK_HIP(hipEventCreateWithFlags(&ctx->prove_fork, hipEventDisableTiming));
+  uint32_t* dv;  // 3 gnb vectors; the first gnb become the h scalars
+  ZK_TRY(ctx->ws.get("g16_hb", 3 * gnb * n * 32, (void**)&dv));
+  uint32_t* zb = nullptr;
+  if (pk->d_bidx) {
+    ZK_TRY(ctx->ws.get("g16_zbb", gnb * pk->nb_c * 32, (void**)&zb));
+    k_gather_scalars<<<dim3((unsigned)((pk->nb_c + 255) / 256), (unsigned)gnb), 256, 0, ctx->stream>>>(
+        dz, pk->d_bidx, pk->nb_c, zb, zstr);
+    ZK_HIP(hipGetLastError());
+  }
+  ZK_HIP(hipEventRecord(ctx->prove_fork, ctx->stream));
+  ZK_TRY(witness_map_many(ctx, dr, dz, zstr, (unsigned)gnb, logn, dv));
+  ctx->msm_fork = ctx->prove_fork;
+  int rc = 0;
+  ctx->lane_next = 1 % nl;
+  rc = msm_batch_submit_shared(ctx, &pk->l_query, 1, 0, dz + l * 8, w, gnb, zsb, &jobs[1]);
+  ctx->lane_next = 0;
+  if (pk->d_bidx) {
+    const zkmi_bases* bq[2] = {pk->b_g1_c, pk->b_g2_c};
+    if (!rc) rc = msm_batch_submit_shared(ctx, bq, 2, 0, zb, pk->nb_c, gnb, pk->nb_c * 32, &jobs[3]);
+    ctx->lane_next = (nl >= 3 ? 2 : 1) % nl;
+    if (!rc) rc = msm_batch_submit_shared(ctx, &pk->a_query, 1, 1, dz + 8, nv - 1, gnb, zsb, &jobs[2]);
+  } else {
+    const zkmi_bases* abq[3] = {pk->a_query, pk->b_g1_query, pk->b_g2_query};
+    if (!rc) rc = msm_batch_submit_shared(ctx, abq, 3, 1, dz + 8, nv - 1, gnb, zsb, &jobs[2]);
+  }
+  ctx->msm_fork = nullptr;  // h forks after the witness map
+  ctx->lane_next = 1 % nl;
+  if (!rc) rc = msm_batch_submit_shared(ctx, &pk->h_query_rev, 1, 0, dv, n - 1, gnb, n * 32, &jobs[0]);
+  return rc;
+}
+
+int groth16_prove_many_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, const uint32_t* dz, size_t nb,
+                              size_t z_stride, const uint64_t* r, const uint64_t* s, zkmi_proof_job** out) {
+  *out = nullptr;
+  size_t l = dr.l, w = dr.w, nv = l + w;
+  uint32_t logn = domain_log(dr.m + l);
+  if (l != pk->num_instance || w != pk->num_witness || ((size_t)1 << logn) != pk->n) {
+    set_error("prove_many: circuit shape (m %zu, l %zu, w %zu) does not match the proving key (n %llu, l %llu, w %llu)",
+              dr.m, l, w, (unsigned long long)pk->n, (unsigned long long)pk->num_instance,
+              (unsigned long long)pk->num_witness);
+    return ZKMI_EINVAL;
+  }
+  if (z_stride < nv * 32 || (z_stride & 31)) {
+    set_error("prove_many: z_stride %zu must be a multiple of 32 and >= %zu", z_stride, nv * 32);
+    return ZKMI_EINVAL;
+  }
+  zkmi_proof_job* mj = new zkmi_proof_job;
+  mj->pk = pk;
+  for (auto*& j : mj->jobs) j = nullptr;
+  mj->many = true;
+  mj->nb = nb;
+  mj->ctx = ctx;
+  mj->dr = &dr;
+  mj->dz = dz;
+  mj->zstr = z_stride / 4;
+  mj->rs.assign(r, r + 4 * nb);
+  mj->ss.assign(s, s + 4 * nb);
+  int rc = 0;
+  if (pk->n <= SMALL_PROOF_MAX) {
+    const size_t G = (size_t)prove_group_size(ctx, pk->n);
+    for (size_t b0 = 0; b0 < nb && !rc; b0 += G) {
+      const size_t gnb = std::min(G, nb - b0);
+      zkmi_proof_job* pj = new zkmi_proof_job;
+      pj->pk = pk;
+      for (auto*& j : pj->jobs) j = nullptr;
+      pj->gnb = gnb;
+      pj->rs.assign(r + 4 * b0, r + 4 * (b0 + gnb));
+      pj->ss.assign(s + 4 * b0, s + 4 * (b0 + gnb));
+      pj->asms.resize(gnb);
+      mj->parts.push_back(pj);
+      rc = prove_group_submit(ctx, pk, dr, dz + b0 * mj->zstr, mj->zstr, gnb, logn, pj);
+      // the key-only part of each assembly while the GPU works
+      for (size_t i = 0; i < gnb && !rc; i++)
+        groth16_asm_fixed_tab(pk->asm_d1.data(), pk->asm_d2.data(), &pj->rs[4 * i], &pj->ss[4 * i], &pj->asms[i]);
+    }
+    mj->next = nb;
+  } else {
+    for (; mj->next < std::min<size_t>(nb, 2) && !rc; mj->next++) {
+      zkmi_proof_job* pj = nullptr;
+      rc = groth16_prove_submit(ctx, pk, dr, dz + mj->next * mj->zstr, r + 4 * mj->next, s + 4 * mj->next, &pj);
+      if (!rc) mj->parts.push_back(pj);
+    }
+  }
+  if (rc) {
+    proof_job_free(mj);
+    return rc;
+  }
+  *out = mj;
+  return 0;
+}
+
+// a group's MSM results -> its gnb proofs (groth16_prove_wait's order of stages)
+static int prove_group_wait(zkmi_proof_job* pj, uint64_t* a_out, uint64_t* b_out, uint64_t* c_out) {
+  const zkmi_pk* pk = pj->pk;
+  zkmi_msm_job** jobs = pj->jobs;
+  const size_t g = pj->gnb;
+  std::vector<uint64_t> h_acc(g * 8), l_acc(g * 8), a_acc(g * 8), b1_acc(g * 8), b2_acc(g * 16);
+  int rc = 0;
+  if (!rc) rc = msm_batch_wait(jobs[1], l_acc.data(), g), jobs[1] = nullptr;
+  if (!rc) rc = msm_batch_wait(jobs[2], a_acc.data(), g), jobs[2] = nullptr;
+  if (!rc) rc = msm_batch_wait(jobs[3], b1_acc.data(), g), jobs[3] = nullptr;
+  for (size_t i = 0; i < g && !rc; i++)
+    groth16_asm_ab(pk->alpha_g1, pk->beta_g1, pk->a0, pk->b1_0, &a_acc[8 * i], &b1_acc[8 * i], &pj->rs[4 * i],
+                   &pj->ss[4 * i], &pj->asms[i]);
+  if (!rc) rc = msm_batch_wait(jobs[4], b2_acc.data(), g), jobs[4] = nullptr;
+  for (size_t i = 0; i < g && !rc; i++)
+    groth16_asm_b(pk->beta_g2, pk->b2_0, &b2_acc[16 * i], &pj->asms[i], b_out + 16 * i);
+  if (!rc) rc = msm_batch_wait(jobs[0], h_acc.data(), g), jobs[0] = nullptr;
+  for (size_t i = 0; i < g && !rc; i++)
+    groth16_asm_c(&l_acc[8 * i], &h_acc[8 * i], &pj->asms[i], a_out + 8 * i, c_out + 8 * i);
+  proof_job_free(pj);
+  return rc;
+}
+
+int groth16_prove_many_wait(zkmi_proof_job* mj, size_t nb, uint64_t* a_out, uint64_t* b_out, uint64_t* c_out) {
+  int rc = 0;
+  size_t at = 0;
+  // (parts grows while it is walked above the small schedule: index, not iterator)
+  for (size_t k = 0; k < mj->parts.size(); k++) {
+    zkmi_proof_job* pj = mj->parts[k];
+    mj->parts[k] = nullptr;
+    if (rc) {
+      proof_job_free(pj);
+      continue;
+    }
+    if (pj->gnb) {
+      const size_t g = pj->gnb;
+      rc = prove_group_wait(pj, a_out + 8 * at, b_out + 16 * at, c_out + 8 * at);
+      at += g;
+    } else {
+      rc = groth16_prove_wait(pj, a_out + 8 * at, b_out + 16 * at, c_out + 8 * at);
+      at++;
+      if (!rc && mj->next < mj->nb) {  // keep two in flight
+        zkmi_proof_job* nx = nullptr;
+        rc = groth16_prove_submit(mj->ctx, mj->pk, *mj->dr, mj->dz + mj->next * mj->zstr, &mj->rs[4 * mj->next],
+                                  &mj->ss[4 * mj->next], &nx);
+        if (!rc) mj->parts.push_back(nx), mj->next++;
+      }
+    }
+  }
+  mj->parts.clear();
+  proof_job_free(mj);
+  return rc;
 }
 
 int groth16_prove(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs* cs, const uint64_t* z, const uint64_t r[4],
@@ -1653,10 +1916,44 @@ int zkmi_groth16_prove_wait(zkmi_proof_job* job, uint64_t a_out[8], uint64_t b_o
     set_error("zkmi_groth16_prove_wait: null argument");
     return ZKMI_EINVAL;
   }
+  if (job->many) {  // the job stays valid
+    set_error("zkmi_groth16_prove_wait: a prove_many job is finished with zkmi_groth16_prove_many_wait");
+    return ZKMI_EINVAL;
+  }
   zkmi_ctx* ctx = job->pk->ctx;
   ZK_DEVICE_GUARD(ctx);
   int rc = groth16_prove_wait(job, a_out, b_out, c_out);
   if (rc == 0) rc = timer_flush(ctx, false);
+  return rc;
+}
+int zkmi_groth16_prove_many_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_dev* cs, const void* d_z,
+                                   size_t nb, size_t z_stride, const uint64_t* r, const uint64_t* s,
+                                   zkmi_proof_job** job) {
+  ZK_DEVICE_GUARD(ctx);
+  if (!ctx || !pk || !cs || !job || (nb && (!d_z || !r || !s))) {
+    set_error("zkmi_groth16_prove_many_submit: null argument");
+    return ZKMI_EINVAL;
+  }
+  return groth16_prove_many_submit(ctx, pk, *cs, (const uint32_t*)d_z, nb, z_stride, r, s, job);
+}
+int zkmi_groth16_prove_many_wait(zkmi_proof_job* job, size_t nb, uint64_t* a_out, uint64_t* b_out, uint64_t* c_out) {
+  if (!job || !job->many || job->nb != nb || (nb && (!a_out || !b_out || !c_out))) {  // the job stays valid
+    set_error("zkmi_groth16_prove_many_wait: not a prove_many job of %zu proofs (or a null output)", nb);
+    return ZKMI_EINVAL;
+  }
+  zkmi_ctx* ctx = job->pk->ctx;
+  ZK_DEVICE_GUARD(ctx);
+  int rc = groth16_prove_many_wait(job, nb, a_out, b_out, c_out);
+  if (rc == 0) rc = timer_flush(ctx, false);
+  return rc;
+}
+int zkmi_groth16_prove_many(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_dev* cs, const void* d_z, size_t nb,
+                            size_t z_stride, const uint64_t* r, const uint64_t* s, uint64_t* a_out, uint64_t* b_out,
+                            uint64_t* c_out) {
+  zkmi_proof_job* job = nullptr;
+  ZK_TRY(zkmi_groth16_prove_many_submit(ctx, pk, cs, d_z, nb, z_stride, r, s, &job));
+  int rc = zkmi_groth16_prove_many_wait(job, nb, a_out, b_out, c_out);
+  if (rc == 0) rc = timer_flush(ctx);
   return rc;
 }
 int zkmi_pk_synthetic(zkmi_ctx* ctx, uint64_t seed, uint32_t log_n, size_t num_instance, size_t num_witness,

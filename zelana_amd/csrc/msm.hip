@@ -193,12 +193,20 @@ __device__ __forceinline__ void scalar_digits(const uint32_t* __restrict__ scala
 // (p = 1, Wp = W without a table).  Digits depend on the scalars only (bases
 // at infinity are skipped in the accumulation), so MSMs with the same
 // scalars over different base sets share one sort (msm_submit_shared).
-template <int C, bool BAL>
+// BAT (batched MSMs, msm_batch_submit): blockIdx.y is the batch; it reads the
+// scalar vector at scalars + batch * sstride words and writes the batch's
+// Wp * p * n digits after those of the batches before it, so the sort sees
+// nb * Wp windows (the batch index is an outer window).
+template <int C, bool BAL, bool BAT = false>
 __global__ void __launch_bounds__(256) k_msm_digits(const uint32_t* __restrict__ scalars, size_t n, int p, int Wp,
-                                                    int32_t* __restrict__ digits) {
+                                                    int32_t* __restrict__ digits, size_t sstride = 0) {
   ZK_TAIL_WAVE();
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (BAT) {
+    scalars += (size_t)blockIdx.y * sstride;
+    digits += (size_t)blockIdx.y * (size_t)Wp * p * n;
+  }
   constexpr int W = msm_windows(C);
   int32_t d[W];
   scalar_digits<C, BAL>(scalars, i, d);
@@ -440,19 +448,24 @@ __device__ __forceinline__ void rs_scalar_keys(const uint32_t* __restrict__ scal
 // Order inside a bucket is then arbitrary, as everywhere (group addition is
 // exact).  Contention stays low: ~30 entries per bucket.
 constexpr size_t SMALL_SORT_MAX = (size_t)1 << 18;
-template <int C, bool BAL>
+// BAT (batched MSMs): blockIdx.y is the batch: its scalars start sstride words
+// further per batch and its keys Wp * B further (the batch is an outer window);
+// values are unchanged (every batch gathers the same table rows).
+template <int C, bool BAL, bool BAT = false>
 __global__ void __launch_bounds__(256) k_ss_count(const uint32_t* __restrict__ scalars, size_t n, int Wp, uint32_t B,
-                                                  uint32_t wsel, uint32_t* __restrict__ cnt) {
+                                                  uint32_t wsel, uint32_t* __restrict__ cnt, size_t sstride = 0) {
   ZK_TAIL_WAVE();
   constexpr int W = msm_windows(C);
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t key[W], val[W];
   bool ok[W];
+  if (BAT) scalars += (size_t)blockIdx.y * sstride;
   rs_scalar_keys<C, BAL>(scalars, i, n, Wp, B, key, val, ok, wsel);
+  const uint32_t koff = BAT ? blockIdx.y * (uint32_t)Wp * B : 0u;
 #pragma unroll
   for (int w = 0; w < W; w++)
-    if (ok[w]) atomicAdd(&cnt[key[w]], 1u);
+    if (ok[w]) atomicAdd(&cnt[key[w] + koff], 1u);
 }
 // one 1024-thread workgroup: bstart[k] = sum of cnt[< k], bstart[K] = total,
 // cursor = a copy of bstart[0..K)
@@ -487,20 +500,22 @@ __global__ void __launch_bounds__(1024) k_ss_scan(uint32_t* __restrict__ cnt, ui
   }
   if (threadIdx.x == 0) bstart[K] = total;
 }
-template <int C, bool BAL>
+template <int C, bool BAL, bool BAT = false>
 __global__ void __launch_bounds__(256) k_ss_scatter(const uint32_t* __restrict__ scalars, size_t n, int Wp,
                                                     uint32_t B, uint32_t wsel, uint32_t* __restrict__ cursor,
-                                                    uint32_t* __restrict__ sval) {
+                                                    uint32_t* __restrict__ sval, size_t sstride = 0) {
   ZK_TAIL_WAVE();
   constexpr int W = msm_windows(C);
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t key[W], val[W];
   bool ok[W];
+  if (BAT) scalars += (size_t)blockIdx.y * sstride;
   rs_scalar_keys<C, BAL>(scalars, i, n, Wp, B, key, val, ok, wsel);
+  const uint32_t koff = BAT ? blockIdx.y * (uint32_t)Wp * B : 0u;
 #pragma unroll
   for (int w = 0; w < W; w++)
-    if (ok[w]) sval[atomicAdd(&cursor[key[w]], 1u)] = val[w];
+    if (ok[w]) sval[atomicAdd(&cursor[key[w] + koff], 1u)] = val[w];
 }
 
 // one workgroup: bin starts and tile starts (tiles of <= C2 entries per bin)
@@ -706,12 +721,16 @@ __device__ __forceinline__ uint32_t block_prefix(uint32_t nb, Get get, uint32_t*
   return total;
 }
 
-template <int C, bool BAL>
+// BAT (batched MSMs): the chunks of batch q are workgroups [q * nfb, (q + 1)
+// * nfb); a chunk reads its batch's scalar vector (sstride words apart) and
+// offsets its keys by batch * Wp * B.  Chunk offsets, super-chunks and bins
+// work on the flat chunk index as before.
+template <int C, bool BAL, bool BAT = false>
 __global__ void __launch_bounds__(256) k_bs_count(const uint32_t* __restrict__ scalars, size_t n, int Wp, uint32_t B,
                                                   uint32_t wsel, uint32_t NH, uint32_t lob, uint32_t CS, uint32_t scs,
                                                   uint32_t* __restrict__ bintot, uint32_t* __restrict__ sctot,
                                                   uint32_t* __restrict__ choff, uint32_t* __restrict__ next_ctr,
-                                                  uint32_t ctr_words) {
+                                                  uint32_t ctr_words, uint32_t nfb = 0, size_t sstride = 0) {
   ZK_TAIL_WAVE();
   extern __shared__ uint32_t hist[];
   constexpr int W = msm_windows(C);
@@ -719,14 +738,17 @@ __global__ void __launch_bounds__(256) k_bs_count(const uint32_t* __restrict__ s
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < ctr_words; i += (size_t)gridDim.x * 256) next_ctr[i] = 0;
   for (uint32_t x = threadIdx.x; x < NH; x += 256) hist[x] = 0;
   __syncthreads();
-  const size_t base = (size_t)blockIdx.x * CS;
+  const uint32_t bq = BAT ? blockIdx.x / nfb : 0u;
+  const size_t base = (size_t)(BAT ? blockIdx.x - bq * nfb : blockIdx.x) * CS;
+  const uint32_t koff = BAT ? bq * (uint32_t)Wp * B : 0u;
+  if (BAT) scalars += (size_t)bq * sstride;
   for (uint32_t k = threadIdx.x; k < CS && base + k < n; k += 256) {
     uint32_t key[W], val[W];
     bool ok[W];
     rs_scalar_keys<C, BAL>(scalars, base + k, n, Wp, B, key, val, ok, wsel);
 #pragma unroll
     for (int w = 0; w < W; w++)
-      if (ok[w]) atomicAdd(&hist[key[w] >> lob], 1u);
+      if (ok[w]) atomicAdd(&hist[(key[w] + koff) >> lob], 1u);
   }
   __syncthreads();
   uint32_t* sc = sctot + (size_t)(blockIdx.x >> scs) * NH;
@@ -742,13 +764,13 @@ __global__ void __launch_bounds__(256) k_bs_count(const uint32_t* __restrict__ s
 }
 
 // T threads, sub-tiles of T scalars (T * W entries)
-template <int C, int T, bool BAL>
+template <int C, int T, bool BAL, bool BAT = false>
 __global__ void __launch_bounds__(T) k_bs_scatter1(const uint32_t* __restrict__ scalars, size_t n, int Wp, uint32_t B,
                                                    uint32_t wsel, uint32_t NH, uint32_t lob, uint32_t CS, uint32_t scs,
                                                    const uint32_t* __restrict__ bintot,
                                                    const uint32_t* __restrict__ sctot,
                                                    const uint32_t* __restrict__ choff, BsKey* __restrict__ okey,
-                                                   uint32_t* __restrict__ oval) {
+                                                   uint32_t* __restrict__ oval, uint32_t nfb = 0, size_t sstride = 0) {
   ZK_TAIL_WAVE();
   extern __shared__ uint32_t lds[];
   constexpr int W = msm_windows(C);
@@ -760,12 +782,19 @@ __global__ void __launch_bounds__(T) k_bs_scatter1(const uint32_t* __restrict__ 
     for (uint32_t q = 0; q < s0; q++) g += sctot[(size_t)q * NH + x];
     gbase[x] = g;
   }
-  const size_t base = (size_t)blockIdx.x * CS;
+  const uint32_t bq = BAT ? blockIdx.x / nfb : 0u;
+  const size_t base = (size_t)(BAT ? blockIdx.x - bq * nfb : blockIdx.x) * CS;
   const uint32_t cnt = (uint32_t)std::min<size_t>(CS, n - base);
+  const uint32_t koff = BAT ? bq * (uint32_t)Wp * B : 0u;
+  if (BAT) scalars += (size_t)bq * sstride;
   auto fill = [&](uint32_t sub, uint32_t* key, uint32_t* val, bool* ok) {
     const uint32_t k = sub * T + threadIdx.x;
     if (k < cnt) {
       rs_scalar_keys<C, BAL>(scalars, base + k, n, Wp, B, key, val, ok, wsel);
+      if (BAT) {
+#pragma unroll
+        for (int w = 0; w < W; w++) key[w] += koff;
+      }
     } else {
 #pragma unroll
       for (int w = 0; w < W; w++) ok[w] = false;
@@ -2586,16 +2615,25 @@ static int pick_window(size_t n) {
   return 17;
 }
 
+// nb = 0: one MSM (the launches of before); nb >= 1: the batched kernels, one
+// grid row per batch, scalar vectors sstride words apart
 template <int C>
-static void launch_digits(hipStream_t st, const uint32_t* sc, size_t n, int p, int Wp, bool bal, int32_t* dg) {
-  if (bal) k_msm_digits<C, true><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(sc, n, p, Wp, dg);
-  else k_msm_digits<C, false><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(sc, n, p, Wp, dg);
+static void launch_digits(hipStream_t st, const uint32_t* sc, size_t n, int p, int Wp, bool bal, int32_t* dg,
+                          uint32_t nb, size_t sstride) {
+  const unsigned g = (unsigned)((n + 255) / 256);
+  if (nb) {
+    if (bal) k_msm_digits<C, true, true><<<dim3(g, nb), 256, 0, st>>>(sc, n, p, Wp, dg, sstride);
+    else k_msm_digits<C, false, true><<<dim3(g, nb), 256, 0, st>>>(sc, n, p, Wp, dg, sstride);
+    return;
+  }
+  if (bal) k_msm_digits<C, true><<<g, 256, 0, st>>>(sc, n, p, Wp, dg);
+  else k_msm_digits<C, false><<<g, 256, 0, st>>>(sc, n, p, Wp, dg);
 }
 static int dispatch_digits(int c, hipStream_t st, const uint32_t* sc, size_t n, int p, int Wp, bool bal,
-                           int32_t* dg) {
+                           int32_t* dg, uint32_t nb = 0, size_t sstride = 0) {
   switch (c) {
 #define ZK_C(CC) \
-  case CC: launch_digits<CC>(st, sc, n, p, Wp, bal, dg); break;
+  case CC: launch_digits<CC>(st, sc, n, p, Wp, bal, dg, nb, sstride); break;
     ZK_C(4) ZK_C(5) ZK_C(6) ZK_C(7) ZK_C(8) ZK_C(9) ZK_C(10) ZK_C(11) ZK_C(12) ZK_C(13) ZK_C(14) ZK_C(15)
     ZK_C(16) ZK_C(17) ZK_C(18) ZK_C(19) ZK_C(20) ZK_C(21) ZK_C(22)
 #undef ZK_C
@@ -2608,19 +2646,27 @@ static int dispatch_digits(int c, hipStream_t st, const uint32_t* sc, size_t n, 
 
 template <int C, bool BAL>
 static void launch_small_sort(hipStream_t st, const uint32_t* sc, size_t n, int Wp, uint32_t B, uint32_t wsel, uint32_t K,
-                              uint32_t* cnt, uint32_t* cursor, uint32_t* bstart, uint32_t* sval) {
+                              uint32_t* cnt, uint32_t* cursor, uint32_t* bstart, uint32_t* sval, uint32_t nb,
+                              size_t sstride) {
   const unsigned g = (unsigned)((n + 255) / 256);
+  if (nb) {  // batched: K covers every batch's windows
+    k_ss_count<C, BAL, true><<<dim3(g, nb), 256, 0, st>>>(sc, n, Wp, B, wsel, cnt, sstride);
+    k_ss_scan<<<1, 1024, 0, st>>>(cnt, K, bstart, cursor);
+    k_ss_scatter<C, BAL, true><<<dim3(g, nb), 256, 0, st>>>(sc, n, Wp, B, wsel, cursor, sval, sstride);
+    return;
+  }
   k_ss_count<C, BAL><<<g, 256, 0, st>>>(sc, n, Wp, B, wsel, cnt);
   k_ss_scan<<<1, 1024, 0, st>>>(cnt, K, bstart, cursor);
   k_ss_scatter<C, BAL><<<g, 256, 0, st>>>(sc, n, Wp, B, wsel, cursor, sval);
 }
 static int small_sort(int c, bool bal, hipStream_t st, const uint32_t* sc, size_t n, int Wp, uint32_t B, uint32_t wsel, uint32_t K,
-                      uint32_t* cnt, uint32_t* cursor, uint32_t* bstart, uint32_t* sval) {
+                      uint32_t* cnt, uint32_t* cursor, uint32_t* bstart, uint32_t* sval, uint32_t nb = 0,
+                      size_t sstride = 0) {
   switch (c) {
 #define ZK_C(CC)                                                                     \
   case CC:                                                                           \
-    if (bal) launch_small_sort<CC, true>(st, sc, n, Wp, B, wsel, K, cnt, cursor, bstart, sval); \
-    else launch_small_sort<CC, false>(st, sc, n, Wp, B, wsel, K, cnt, cursor, bstart, sval);    \
+    if (bal) launch_small_sort<CC, true>(st, sc, n, Wp, B, wsel, K, cnt, cursor, bstart, sval, nb, sstride); \
+    else launch_small_sort<CC, false>(st, sc, n, Wp, B, wsel, K, cnt, cursor, bstart, sval, nb, sstride);    \
     break;
     ZK_C(12) ZK_C(13) ZK_C(14) ZK_C(15) ZK_C(16) ZK_C(17) ZK_C(18) ZK_C(19) ZK_C(20) ZK_C(21) ZK_C(22)
 #undef ZK_C
@@ -2654,6 +2700,15 @@ struct zkmi_msm_job {
   // failure exchange (in wait order, as the peers' exchanges) and returns this
   int fail_rc = 0;
   std::string fail_msg;
+  // Batched MSMs (zkmi_msm_batch_submit).  A group job (nbat >= 1) is one
+  // launch sequence over nbat scalar vectors: W = nbat x the single plan's
+  // windows, the bit sums of vector i in windows [i W / nbat, (i + 1) W / nbat).
+  // The job handed to the caller (batch) owns the group jobs of its nb vectors
+  // in order; it has no GPU work of its own.
+  int nbat = 0;
+  bool batch = false;
+  size_t nb = 0;
+  std::vector<zkmi_msm_job*> parts;
 };
 
 namespace zk {
@@ -2690,7 +2745,13 @@ struct MsmPlan {
   // msm_windows(c) the scalars recode into (wsel as rs_scalar_keys)
   int w0 = 0;
   uint32_t wsel = 0;
-  int Wp() const { return wsel ? msm_windows(c) : W; }  // windows per recoded scalar (per table copy)
+  // batched plans (msm_plan_batch): nb scalar vectors, sstride words apart, as
+  // nb x the single plan's windows: W, K and Mmax cover every batch, ne is
+  // still one window's entries
+  int nb = 1;
+  bool batch = false;
+  size_t sstride = 0;
+  int Wp() const { return wsel ? msm_windows(c) : W / nb; }  // windows per recoded scalar (per table copy)
 };
 static MsmPlan msm_plan(const zkmi_ctx* ctx, const zkmi_bases* tb, size_t n) {
   MsmPlan P;
@@ -2707,6 +2768,20 @@ static MsmPlan msm_plan(const zkmi_ctx* ctx, const zkmi_bases* tb, size_t n) {
   P.bb = P.c - 1;
   P.lb = (P.bb + 1) / 2;
   P.hb = P.bb - P.lb;
+  return P;
+}
+// The single plan with the batch index as an outer window (key = (batch * W +
+// window) * B + ...): nb x the windows, buckets and entries; everything after
+// the sort works per key and per window, so it runs unchanged on the larger
+// plan and leaves nb independent sets of bit sums.
+static MsmPlan msm_plan_batch(const zkmi_ctx* ctx, const zkmi_bases* tb, size_t n, int nb, size_t sstride) {
+  MsmPlan P = msm_plan(ctx, tb, n);
+  P.batch = true;
+  P.nb = nb;
+  P.sstride = sstride;
+  P.W *= nb;
+  P.K *= (uint32_t)nb;
+  P.Mmax *= (size_t)nb;
   return P;
 }
 static bool same_plan(const MsmPlan& a, const MsmPlan& b) {
@@ -2746,6 +2821,7 @@ static uint32_t item_cap(const zkmi_ctx* ctx, const MsmPlan& P) {
 // same stream), so a sort needs no memset launch.
 struct BsGeom {
   uint32_t lob, NLO, NH, CS, nf, scs, C2, T2max;
+  uint32_t nfb;  // chunks per scalar vector (nf = nfb x the plan's batches)
   size_t nmain;  // items: NH * NLO main slots
   size_t ctr_words() const { return (size_t)NH + 16 + (size_t)BS_NSC * NH + 2 * (ITEM_CAP_MAX + 1); }
   uint32_t* ghist(uint32_t* ctr) const { return ctr + NH + 16 + (size_t)BS_NSC * NH; }
@@ -2760,7 +2836,8 @@ static BsGeom bs_geom(const MsmPlan& P, size_t n) {
   g.NLO = 1u << g.lob;
   g.NH = (P.K + g.NLO - 1) >> g.lob;
   g.CS = 1024u * (uint32_t)std::max<size_t>(1, (n + 1024ull * 2048 - 1) / (1024ull * 2048));
-  g.nf = (uint32_t)std::max<size_t>(1, (n + g.CS - 1) / g.CS);
+  g.nfb = (uint32_t)std::max<size_t>(1, (n + g.CS - 1) / g.CS);
+  g.nf = g.nfb * (uint32_t)P.nb;
   g.scs = 0;
   while (((size_t)g.nf + (1u << g.scs) - 1) >> g.scs > BS_NSC) g.scs++;
   const size_t C2B = P.Mmax < ((size_t)1 << 22) ? 4096 : 16384;  // small sorts: more, shorter tiles
@@ -2775,10 +2852,21 @@ static size_t bs_lds_scatter2(const BsGeom& g) { return rs_scatter_lds(g.NLO, BS
 template <int C, bool BAL>
 static void launch_bs_p1(hipStream_t st, const uint32_t* sc, size_t n, int Wp, uint32_t B, uint32_t wsel, const BsGeom& g,
                          uint32_t* ctr, uint32_t* next_ctr, uint32_t* choff, uint32_t* okey, uint32_t* oval,
-                         bool scatter) {
+                         bool scatter, bool batch, size_t sstride) {
   constexpr int W = msm_windows(C);
   uint32_t* bintot = ctr;
   uint32_t* sctot = ctr + g.NH + 16;
+  if (batch) {
+    if (scatter)
+      k_bs_scatter1<C, 256, BAL, true><<<g.nf, 256, rs_scatter_lds(g.NH, 256 * W, 256), st>>>(
+          sc, n, Wp, B, wsel, g.NH, g.lob, g.CS, g.scs, bintot, sctot, choff, reinterpret_cast<BsKey*>(okey), oval,
+          g.nfb, sstride);
+    else
+      k_bs_count<C, BAL, true><<<g.nf, 256, g.NH * 4, st>>>(sc, n, Wp, B, wsel, g.NH, g.lob, g.CS, g.scs, bintot,
+                                                            sctot, choff, next_ctr, (uint32_t)g.ctr_words(), g.nfb,
+                                                            sstride);
+    return;
+  }
   if (scatter)
     k_bs_scatter1<C, 256, BAL><<<g.nf, 256, rs_scatter_lds(g.NH, 256 * W, 256), st>>>(
         sc, n, Wp, B, wsel, g.NH, g.lob, g.CS, g.scs, bintot, sctot, choff, reinterpret_cast<BsKey*>(okey), oval);
@@ -2787,12 +2875,13 @@ static void launch_bs_p1(hipStream_t st, const uint32_t* sc, size_t n, int Wp, u
                                                     next_ctr, (uint32_t)g.ctr_words());
 }
 static int bs_p1(int c, bool bal, hipStream_t st, const uint32_t* sc, size_t n, int Wp, uint32_t B, uint32_t wsel, const BsGeom& g,
-                 uint32_t* ctr, uint32_t* next_ctr, uint32_t* choff, uint32_t* okey, uint32_t* oval, bool scatter) {
+                 uint32_t* ctr, uint32_t* next_ctr, uint32_t* choff, uint32_t* okey, uint32_t* oval, bool scatter,
+                 bool batch = false, size_t sstride = 0) {
   switch (c) {
 #define ZK_C(CC)                                                                                  \
   case CC:                                                                                        \
-    if (bal) launch_bs_p1<CC, true>(st, sc, n, Wp, B, wsel, g, ctr, next_ctr, choff, okey, oval, scatter); \
-    else launch_bs_p1<CC, false>(st, sc, n, Wp, B, wsel, g, ctr, next_ctr, choff, okey, oval, scatter);    \
+    if (bal) launch_bs_p1<CC, true>(st, sc, n, Wp, B, wsel, g, ctr, next_ctr, choff, okey, oval, scatter, batch, sstride); \
+    else launch_bs_p1<CC, false>(st, sc, n, Wp, B, wsel, g, ctr, next_ctr, choff, okey, oval, scatter, batch, sstride);    \
     break;
     ZK_C(12) ZK_C(13) ZK_C(14) ZK_C(15) ZK_C(16) ZK_C(17) ZK_C(18) ZK_C(19) ZK_C(20) ZK_C(21) ZK_C(22)
 #undef ZK_C
@@ -2903,8 +2992,10 @@ static int msm_sort_phase(zkmi_ctx* ctx, MsmLane* lane, const MsmPlan& P, const 
       io.split = split;
       io.stage = stage;
     }
-    ZK_TRY(bs_p1(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, g, ctr, next_ctr, choff, okey, oval, false));
-    ZK_TRY(bs_p1(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, g, ctr, next_ctr, choff, okey, oval, true));
+    ZK_TRY(bs_p1(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, g, ctr, next_ctr, choff, okey, oval, false, P.batch,
+                 P.sstride));
+    ZK_TRY(bs_p1(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, g, ctr, next_ctr, choff, okey, oval, true, P.batch,
+                 P.sstride));
     ZK_HIP(hipEventRecord(lane->consumed, st));
     ZK_HIP(hipStreamWaitEvent(ctx->stream, lane->consumed, 0));
     const uint32_t gt = ((g.T2max + 7) / 8) * 8;  // XCD-mapped grid (rs_xcd_tile)
@@ -2938,7 +3029,8 @@ static int msm_sort_phase(zkmi_ctx* ctx, MsmLane* lane, const MsmPlan& P, const 
       lane->ss_clean_words = P.K;
     }
     lane->ss_clean = nullptr;  // until every kernel of this sort is queued
-    ZK_TRY(small_sort(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, P.K, scnt, scur, bstart, sval));
+    ZK_TRY(small_sort(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, P.K, scnt, scur, bstart, sval,
+                      P.batch ? (uint32_t)P.nb : 0u, P.sstride));
     lane->ss_clean = scnt;
     ZK_HIP(hipEventRecord(lane->consumed, st));
     ZK_HIP(hipStreamWaitEvent(ctx->stream, lane->consumed, 0));
@@ -2955,7 +3047,8 @@ static int msm_sort_phase(zkmi_ctx* ctx, MsmLane* lane, const MsmPlan& P, const 
   ZK_TRY(ws.get("msm_bsums", ((std::max(len1, len2) + 1023) / 1024) * 4 + 16, (void**)&bsums));
   ZK_TRY(ws.get("msm_tot", 64, (void**)&tot));
   {
-    ZK_TRY(dispatch_digits(P.c, st, d_scalars, n, P.p, P.W, P.bal, digits));
+    ZK_TRY(dispatch_digits(P.c, st, d_scalars, n, P.p, P.batch ? P.Wp() : P.W, P.bal, digits,
+                           P.batch ? (uint32_t)P.nb : 0u, P.sstride));
     ZK_HIP(hipEventRecord(lane->consumed, st));
     ZK_HIP(hipStreamWaitEvent(ctx->stream, lane->consumed, 0));
   }
@@ -3381,6 +3474,8 @@ int msm_submit_shared(zkmi_ctx* ctx, const zkmi_bases* const* bs, int k, size_t 
 // overwritten by the stale copy.
 void msm_job_free(zkmi_msm_job* job) {
   if (!job) return;
+  for (zkmi_msm_job* part : job->parts) msm_job_free(part);
+  job->parts.clear();
   // (the event, not the stream: a lane released by zkmi_comm_init after its
   // work -- comm.hip stream budget -- may be gone while its jobs are unwaited)
   if (job->host && job->st) {
@@ -3397,6 +3492,10 @@ void msm_job_free(zkmi_msm_job* job) {
 int msm_wait(zkmi_msm_job* job, uint64_t* out) {
   if (!job) {
     set_error("msm_wait: null job");
+    return ZKMI_EINVAL;
+  }
+  if (job->batch || job->nbat) {  // the job stays valid
+    set_error("msm_wait: a batch job is finished with zkmi_msm_batch_wait");
     return ZKMI_EINVAL;
   }
   zkmi_ctx* ctx = job->ctx;
@@ -3527,6 +3626,138 @@ int msm_device(zkmi_ctx* ctx, const zkmi_bases* b, size_t offset, const void* d_
   zkmi_msm_job* job;
   ZK_TRY(msm_submit(ctx, b, offset, d_scalars, n, &job));
   return msm_wait(job, out_affine);
+}
+
+// ------------------------------------------------------------ batched MSMs
+// nb scalar vectors over one base set and range (zkmi_msm_batch_submit): the
+// vectors are split into groups of at most G; a group is ONE launch sequence
+// over the plan msm_plan_batch makes of it, on the next lane, so groups
+// pipeline the way consecutive MSMs do.  A group of one runs the single-MSM
+// path as it is.
+//
+// Group size: zkmi_ctx_set_batch_group, or BATCH_GROUP_AUTO; then the largest
+// g <= that for which the batched plan keeps K' <= BATCH_K_MAX buckets and
+// Mmax' <= BATCH_M_MAX entries (sort workspace 4 arrays x Mmax' x 4 B <= 1 GB
+// per lane, inside check_size's 2^32) and does not take the one-lane-per-bucket
+// (items) path: a plan that takes that path alone already fills the part, and
+// its item geometry is sized for one or two windows, so such MSMs run as
+// pipelined single MSMs (g = 1).
+constexpr int BATCH_GROUP_AUTO = 16;
+constexpr uint32_t BATCH_K_MAX = 1u << 20;
+constexpr size_t BATCH_M_MAX = (size_t)1 << 26;
+static int msm_batch_group(const zkmi_ctx* ctx, const zkmi_bases* b, size_t n, size_t nb) {
+  int g = ctx->batch_group > 0 ? ctx->batch_group : BATCH_GROUP_AUTO;
+  if ((size_t)g > nb) g = (int)nb;
+  if (g < 1) g = 1;
+  const MsmPlan P1 = msm_plan(ctx, b, n);
+  if (items_plan(P1)) return 1;
+  for (; g > 1; g--) {
+    if ((uint64_t)P1.K * g > BATCH_K_MAX || P1.Mmax * (size_t)g > BATCH_M_MAX) continue;
+    if (!items_plan(msm_plan_batch(ctx, b, n, g, 0))) break;
+  }
+  return g;
+}
+
+int msm_batch_submit_shared(zkmi_ctx* ctx, const zkmi_bases* const* bs, int k, size_t offset, const void* d_scalars,
+                            size_t n, size_t nb, size_t stride, zkmi_msm_job** jobs) {
+  for (int i = 0; i < k; i++) jobs[i] = nullptr;
+  for (int i = 0; i < k; i++) ZK_TRY(check_range(bs[i], offset, n));
+  if (stride < n * 32 || (stride & 31) || (n && nb && !d_scalars)) {
+    set_error("msm_batch: stride %zu must be a multiple of 32 and >= n * 32 = %zu (and the scalars non-null)", stride,
+              n * 32);
+    return ZKMI_EINVAL;
+  }
+  for (int i = 0; i < k; i++) {
+    const MsmPlan P = msm_plan(ctx, bs[i], n);
+    jobs[i] = new zkmi_msm_job{ctx, bs[i]->g2, P.c, P.W, P.bb, nullptr, 0, nullptr, n == 0 || nb == 0};
+    jobs[i]->batch = true;
+    jobs[i]->nb = nb;
+  }
+  if (n == 0 || nb == 0) return 0;
+  int G = msm_batch_group(ctx, bs[0], n, nb);
+  for (int i = 1; i < k; i++) G = std::min(G, msm_batch_group(ctx, bs[i], n, nb));
+  const size_t sstride = stride / 4;  // u32 words between two scalar vectors
+  int rc = 0;
+  for (size_t b0 = 0; b0 < nb && !rc; b0 += (size_t)G) {
+    const int gb = (int)std::min<size_t>((size_t)G, nb - b0);
+    const uint32_t* sc = (const uint32_t*)d_scalars + b0 * sstride;
+    MsmLane* lane = nullptr;
+    std::vector<bool> done(k, false);
+    for (int i = 0; i < k && !rc; i++) {
+      if (done[i]) continue;
+      const MsmPlan P = gb > 1 ? msm_plan_batch(ctx, bs[i], n, gb, sstride) : msm_plan(ctx, bs[i], n);
+      if ((rc = check_size(P, n))) break;
+      if ((rc = get_lane(ctx, &lane))) break;
+      uint32_t *sval, *bstart;
+      if ((rc = msm_sort_phase(ctx, lane, P, sc, n, &sval, &bstart))) break;
+      for (int j = i; j < k && !rc; j++) {
+        if (done[j] || (j > i && !same_plan(msm_plan(ctx, bs[i], n), msm_plan(ctx, bs[j], n)))) continue;
+        zkmi_msm_job* part = new_job(ctx, bs[j], P, n);
+        part->nbat = gb;
+        jobs[j]->parts.push_back(part);  // owned from here on, whatever follows
+        done[j] = true;
+        rc = msm_acc_any(ctx, lane, P, bs[j], offset, n, sval, bstart, part);
+      }
+    }
+  }
+  if (rc) {
+    for (int i = 0; i < k; i++) {
+      msm_job_free(jobs[i]);
+      jobs[i] = nullptr;
+    }
+  }
+  return rc;
+}
+
+// one group job: the bit sums of its nbat vectors -> nbat points
+static int msm_part_wait(zkmi_msm_job* job, uint64_t* out) {
+  zkmi_ctx* ctx = job->ctx;
+  hipError_t e = hipEventSynchronize(job->done);
+  if (e != hipSuccess) {
+    set_error("msm_batch_wait: %s", hipGetErrorString(e));
+    job->host = nullptr;  // copy state unknown: never recycle the buffer
+    msm_job_free(job);
+    return ZKMI_EHIP;
+  }
+  job->st = nullptr;  // the bit-sum copy has landed
+  int rc = timer_flush(ctx, false);
+  auto th0 = std::chrono::steady_clock::now();
+  // each vector's own W windows; never a Horner pass across the whole job
+  msm_host_batch_combine(job->host, job->nbat, job->g2, job->c, job->W / job->nbat, job->bb, job->sb, out);
+  if (ctx->timer.enabled) {
+    auto& t = ctx->timer.totals["msm_host_epilogue"];
+    t.first += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
+    t.second += 1;
+  }
+  msm_job_free(job);
+  return rc;
+}
+
+int msm_batch_wait(zkmi_msm_job* job, uint64_t* out, size_t nb) {
+  if (!job || !job->batch || job->nb != nb) {  // the job stays valid
+    set_error(!job ? "msm_batch_wait: null job"
+                   : !job->batch ? "msm_batch_wait: not a batch job (finish it with zkmi_msm_wait)"
+                                 : "msm_batch_wait: the job holds another number of MSMs");
+    return ZKMI_EINVAL;
+  }
+  ZK_DEVICE_GUARD(job->ctx);
+  const size_t PW = job->g2 ? 16 : 8;  // u64 per point
+  int rc = 0;
+  if (job->empty) {
+    memset(out, 0, nb * PW * 8);
+  } else {
+    size_t at = 0;
+    for (zkmi_msm_job*& part : job->parts) {
+      const size_t cnt = (size_t)part->nbat;
+      if (!rc) rc = msm_part_wait(part, out + at * PW);
+      else msm_job_free(part);
+      part = nullptr;
+      at += cnt;
+    }
+    job->parts.clear();
+  }
+  msm_job_free(job);
+  return rc;
 }
 
 // Point-sharded MSM (zkmi.h, multi-GPU): every rank runs its shard through

@@ -145,6 +145,14 @@ void msm_host_assemble_combine(const uint32_t* src, size_t stride, size_t skip, 
   else combine<HFq2, 16>(all.data(), nbits, W, c, sb * nseg, out);
 }
 
+void msm_host_batch_combine(const uint32_t* sums, int nb, int g2, int c, int W, int bb, int sb, uint64_t* out) {
+  const size_t per = (size_t)W * (bb + 1) * sb * (g2 ? 64 : 32);  // words of one batch's bit sums
+  const int live = 0;
+  for (int b = 0; b < nb; b++)
+    msm_host_assemble_combine(sums + (size_t)b * per, per, 0, &live, 1, false, g2, c, W, bb, sb,
+                              out + (size_t)b * (g2 ? 16 : 8));
+}
+
 void host_g1_add_affine(const uint64_t a[8], const uint64_t b[8], uint64_t out[8]) {
   auto r = xyzz_add(from_aff_canon<HFq, 4>(a), from_aff_canon<HFq, 4>(b));
   to_affine<HFq, 8>(r, out);

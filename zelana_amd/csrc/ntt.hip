@@ -342,12 +342,23 @@ __device__ __forceinline__ Fe ntt_tab_scale(Fe v, uint64_t i, const NttIo& io) {
 // 1024-element tiles in radix-4 rounds (36 KB LDS, <= 128 VGPRs: 4 waves/SIMD
 // to hide the load and twiddle latency the 2-wave form exposes).
 
-template <bool DIT, int PRO, int EPI, bool PERM, int TB, int RB>
+// BAT (batched transforms, ntt_batch_*): blockIdx.y selects the vector; vector
+// v of src / dst starts v * sstr / v * dstr words after the first.  Twiddles,
+// the group plan and the coset tables are shared.
+struct NttBatch {
+  size_t sstr, dstr;
+};
+template <bool DIT, int PRO, int EPI, bool PERM, int TB, int RB, bool BAT = false>
 __global__ void __launch_bounds__(1 << (TB - RB), (RB == 3 ? 2 : 4) * 256 / (1 << (TB - RB))) k_ntt_group(const uint32_t* src, uint32_t* dst,
                                                                           const uint32_t* __restrict__ tw, uint32_t logn,
-                                                                          uint32_t a, uint32_t k, NttIo io) {
+                                                                          uint32_t a, uint32_t k, NttIo io,
+                                                                          NttBatch bat = NttBatch{0, 0}) {
   constexpr int TILE = 1 << TB, EPT = 1 << RB;
   extern __shared__ __align__(16) uint32_t lds[];  // [limb][slot]
+  if (BAT) {
+    src += (size_t)blockIdx.y * bat.sstr;
+    dst += (size_t)blockIdx.y * bat.dstr;
+  }
   NttGroup g;
   g.logn = logn;
   g.a = a;
@@ -435,11 +446,14 @@ __global__ void __launch_bounds__(1 << (TB - RB), (RB == 3 ? 2 : 4) * 256 / (1 <
 }
 
 // small transforms (n < 2048): one workgroup, all stages in LDS
+// (the kernels below take `vstr`, the words between two vectors of a batched
+// launch, whose grid row blockIdx.y is the vector; single launches pass 0)
 template <bool DIT>
 __global__ void __launch_bounds__(256) k_ntt_small(uint32_t* __restrict__ data, const uint32_t* __restrict__ tw,
-                                                   uint32_t logn) {
+                                                   uint32_t logn, size_t vstr = 0) {
   extern __shared__ __align__(16) uint32_t lds[];
   const uint32_t n = 1u << logn;
+  data += (size_t)blockIdx.y * vstr;
   for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) {
     Fe v = ld_fe(data + (size_t)e * 8);
 #pragma unroll
@@ -507,8 +521,9 @@ __device__ __forceinline__ Fe bitrev_scale(Fe v, uint64_t i, const BitrevScale& 
   return v;
 }
 __global__ void __launch_bounds__(256) k_bitrev_tiled(uint32_t* __restrict__ data, uint32_t logn, uint32_t b,
-                                                      BitrevScale sc) {
+                                                      BitrevScale sc, size_t vstr = 0) {
   extern __shared__ __align__(16) uint32_t lds[];  // two tiles [hi][lo][8]
+  data += (size_t)blockIdx.y * vstr;
   const uint32_t T = 1u << b, midbits = logn - 2 * b;
   const uint32_t mid = blockIdx.x;
   const uint32_t rmid = midbits ? brev_bits(mid, midbits) : 0;
@@ -543,10 +558,13 @@ __global__ void __launch_bounds__(256) k_bitrev_tiled(uint32_t* __restrict__ dat
     }
   }
 }
+// (batched: vector v of `in` at v * vstr words, of `out` -- packed scratch -- at v << logn elements)
 __global__ void __launch_bounds__(256) k_bitrev_naive(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
-                                                      uint32_t logn, BitrevScale sc) {
+                                                      uint32_t logn, BitrevScale sc, size_t vstr = 0) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (1u << logn)) return;
+  in += (size_t)blockIdx.y * vstr;
+  out += ((size_t)blockIdx.y << logn) * 8;
   uint32_t r = logn ? brev_bits(i, logn) : 0;
   st_fe(out + (size_t)r * 8, reduce<FrP>(bitrev_scale(ld_fe(in + (size_t)i * 8), r, sc)));
 }
@@ -554,9 +572,10 @@ __global__ void __launch_bounds__(256) k_bitrev_naive(const uint32_t* __restrict
 // data[i] *= g^i in natural order (forward coset), g^i = lo[i mod 2^KB] * hi[i >> KB]
 __global__ void __launch_bounds__(256) k_ntt_coset_scale(uint32_t* __restrict__ data, uint32_t logn,
                                                          const uint32_t* __restrict__ lo,
-                                                         const uint32_t* __restrict__ hi) {
+                                                         const uint32_t* __restrict__ hi, size_t vstr = 0) {
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= (1ull << logn)) return;
+  data += (size_t)blockIdx.y * vstr;
   Fe v = mul<FrP>(ld_fe(data + i * 8), ld_fe(lo + (i & ((1u << COSET_KB) - 1)) * 8));
   st_fe(data + i * 8, mul<FrP>(v, ld_fe(hi + (i >> COSET_KB) * 8)));
 }
@@ -564,9 +583,10 @@ __global__ void __launch_bounds__(256) k_ntt_coset_scale(uint32_t* __restrict__ 
 // x[p] *= lo[i] * hi[i] at natural index i = rev(p), canonical out (small n)
 __global__ void __launch_bounds__(256) k_scale_rev_small(uint32_t* __restrict__ data, uint32_t logn,
                                                          const uint32_t* __restrict__ lo,
-                                                         const uint32_t* __restrict__ hi) {
+                                                         const uint32_t* __restrict__ hi, size_t vstr = 0) {
   size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (p >= (1ull << logn)) return;
+  data += (size_t)blockIdx.y * vstr;
   uint32_t e = logn ? (__brev((uint32_t)p) >> (32 - logn)) : 0;
   Fe v = mul<FrP>(ld_fe(data + p * 8), ld_fe(lo + (size_t)(e & ((1u << COSET_KB) - 1)) * 8));
   st_fe(data + p * 8, reduce<FrP>(mul<FrP>(v, ld_fe(hi + (size_t)(e >> COSET_KB) * 8))));
@@ -624,10 +644,17 @@ static std::vector<uint32_t> ntt_groups(uint32_t logn) {
 #define ZK_NTT_TB_OUTER 10
 #endif
 static_assert(!ZK_NTT_TW_L8P || ZK_NTT_TB_OUTER == 10, "the limb-8 layout assumes 1024-element outer tiles");
+// nb = 0: one vector (the launch of before); nb >= 1: nb vectors, bat words apart
 template <bool DIT, int PRO, int EPI, bool PERM>
 static void launch_group(hipStream_t st, const uint32_t* src, uint32_t* dst, const uint32_t* tw, uint32_t logn,
-                         uint32_t a, uint32_t k, const NttIo& io) {
+                         uint32_t a, uint32_t k, const NttIo& io, unsigned nb = 0, NttBatch bat = NttBatch{0, 0}) {
   constexpr int TBo = ZK_NTT_TB_OUTER;
+  if (nb) {  // batched: the 1024-element tile shape, one grid row per vector
+    const size_t sm = (size_t)1024 * NL * 4;
+    const dim3 grid((unsigned)((1ull << logn) / 1024), nb);
+    k_ntt_group<DIT, PRO, EPI, PERM, 10, 2, true><<<grid, 256, sm, st>>>(src, dst, tw, logn, a, k, io, bat);
+    return;
+  }
   if (TBo != 10 && !PERM && a > k && logn >= (uint32_t)TBo && k <= (uint32_t)TBo - 2) {  // a pass with column bits
     const size_t sm = ((size_t)1 << TBo) * NL * 4;
     const unsigned grid = (unsigned)((1ull << logn) >> TBo);
@@ -642,8 +669,9 @@ static void launch_group(hipStream_t st, const uint32_t* src, uint32_t* dst, con
 // in-place transform in the requested order without scaling:
 // dit=false: natural in -> bit-reversed out; dit=true: bit-reversed in -> natural out
 // epi (DIF only): 0 none, 2 = x * lo[i] * hi[i] at natural index i, canonical out
-int ntt_raw_epi(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, int epi, const uint32_t* lo,
-                const uint32_t* hi) {
+// nb = 0: one vector; nb >= 1: the batched launches over nb vectors vstr words apart
+int ntt_raw_epi_n(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, int epi, const uint32_t* lo,
+                  const uint32_t* hi, unsigned nb, size_t vstr) {
   const uint32_t* tw;
   ZK_TRY(get_twiddles(ctx, logn, inv, &tw));
   hipStream_t st = ctx->stream;
@@ -651,12 +679,13 @@ int ntt_raw_epi(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, in
   if ((1u << logn) < (uint32_t)NTT_TILE && logn < 11) {
     size_t sm = ((size_t)1 << logn) * NL * 4;
     ScopedKernelTimer tm(ctx, "ntt_small");
-    if (dit) k_ntt_small<true><<<1, 256, sm, st>>>(d, tw, logn);
-    else k_ntt_small<false><<<1, 256, sm, st>>>(d, tw, logn);
+    const unsigned gy = nb ? nb : 1;
+    if (dit) k_ntt_small<true><<<dim3(1, gy), 256, sm, st>>>(d, tw, logn, vstr);
+    else k_ntt_small<false><<<dim3(1, gy), 256, sm, st>>>(d, tw, logn, vstr);
     ZK_HIP(hipGetLastError());
     if (epi) {
       ScopedKernelTimer tm2(ctx, "ntt_scale");
-      k_scale_rev_small<<<(unsigned)(((1ull << logn) + 255) / 256), 256, 0, st>>>(d, logn, lo, hi);
+      k_scale_rev_small<<<dim3((unsigned)(((1ull << logn) + 255) / 256), gy), 256, 0, st>>>(d, logn, lo, hi, vstr);
       ZK_HIP(hipGetLastError());
     }
     return 0;
@@ -664,12 +693,13 @@ int ntt_raw_epi(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, in
   const std::vector<uint32_t> ks = ntt_groups(logn);
   const int ng = (int)ks.size();
   const NttIo io{lo, hi, nullptr};
+  const NttBatch bat{vstr, vstr};
   if (!dit) {
     uint32_t a = logn;
     for (int g = 0; g < ng; g++) {
       ScopedKernelTimer tm(ctx, "ntt_group");
-      if (g == ng - 1 && epi == 2) launch_group<false, 0, 2, false>(st, d, d, tw, logn, a, ks[g], io);
-      else launch_group<false, 0, 0, false>(st, d, d, tw, logn, a, ks[g], io);
+      if (g == ng - 1 && epi == 2) launch_group<false, 0, 2, false>(st, d, d, tw, logn, a, ks[g], io, nb, bat);
+      else launch_group<false, 0, 0, false>(st, d, d, tw, logn, a, ks[g], io, nb, bat);
       a -= ks[g];
     }
   } else {
@@ -677,29 +707,39 @@ int ntt_raw_epi(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, in
     for (int g = ng - 1; g >= 0; g--) {
       a += ks[g];
       ScopedKernelTimer tm(ctx, "ntt_group");
-      launch_group<true, 0, 0, false>(st, d, d, tw, logn, a, ks[g], io);
+      launch_group<true, 0, 0, false>(st, d, d, tw, logn, a, ks[g], io, nb, bat);
     }
   }
   ZK_HIP(hipGetLastError());
   return 0;
+}
+int ntt_raw_epi(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, int epi, const uint32_t* lo,
+                const uint32_t* hi) {
+  return ntt_raw_epi_n(ctx, d, logn, inv, dit, epi, lo, hi, 0, 0);
 }
 int ntt_raw(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit) {
   return ntt_raw_epi(ctx, d, logn, inv, dit, 0, nullptr, nullptr);
 }
 
 // in-place permutation natural <-> bit-reversed (+ optional scaling, + full reduction)
-static int ntt_bitrev_scaled(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, BitrevScale sc) {
+static int ntt_bitrev_scaled(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, BitrevScale sc, unsigned nb = 0,
+                             size_t vstr = 0) {
   hipStream_t st = ctx->stream;
   ScopedKernelTimer tm(ctx, "ntt_bitrev");
+  const unsigned gy = nb ? nb : 1;
   if (logn >= 10) {
     uint32_t b = 5;
     unsigned grid = 1u << (logn - 2 * b);
-    k_bitrev_tiled<<<grid, 256, 2 * (1u << (2 * b)) * 32, st>>>(d, logn, b, sc);
+    k_bitrev_tiled<<<dim3(grid, gy), 256, 2 * (1u << (2 * b)) * 32, st>>>(d, logn, b, sc, vstr);
   } else {
     uint32_t* tmp;
-    ZK_TRY(ctx->ws.get("ntt_tmp_small", ((size_t)1 << logn) * 32, (void**)&tmp));
-    k_bitrev_naive<<<((1u << logn) + 255) / 256, 256, 0, st>>>(d, tmp, logn, sc);
-    ZK_HIP(hipMemcpyAsync(d, tmp, ((size_t)1 << logn) * 32, hipMemcpyDeviceToDevice, st));
+    const size_t vb = ((size_t)1 << logn) * 32;
+    ZK_TRY(ctx->ws.get("ntt_tmp_small", gy * vb, (void**)&tmp));
+    k_bitrev_naive<<<dim3(((1u << logn) + 255) / 256, gy), 256, 0, st>>>(d, tmp, logn, sc, vstr);
+    // (batched: the packed scratch vectors back to their strided places; the
+    // bytes between two vectors are not written)
+    if (nb) ZK_HIP(hipMemcpy2DAsync(d, vstr * 4, tmp, vb, vb, nb, hipMemcpyDeviceToDevice, st));
+    else ZK_HIP(hipMemcpyAsync(d, tmp, vb, hipMemcpyDeviceToDevice, st));
   }
   ZK_HIP(hipGetLastError());
   return 0;
@@ -717,6 +757,11 @@ int ntt_bitrev(zkmi_ctx* ctx, uint32_t* d, uint32_t logn) {
 // Small transforms (one tile or less) keep the single-workgroup kernel and
 // a separate bit reversal.
 int ntt_device(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inverse, int coset) {
+  return ntt_device_n(ctx, d, logn, inverse, coset, 0, 0);
+}
+// nb = 0: one vector; nb >= 1: nb vectors vstr words apart, one launch
+// sequence (the scratch of the out-of-place passes holds nb packed vectors)
+int ntt_device_n(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inverse, int coset, unsigned nb, size_t vstr) {
   if (logn > 28) {
     set_error("ntt: log_n %u > 28 (two-adicity of Fr)", logn);
     return ZKMI_EINVAL;
@@ -727,21 +772,22 @@ int ntt_device(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inverse, int coset
     if (!inverse) {
       if (coset) {
         ScopedKernelTimer tm(ctx, "ntt_scale");
-        k_ntt_coset_scale<<<(unsigned)(((1ull << logn) + 255) / 256), 256, 0, ctx->stream>>>(d, logn, dc.lo_g,
-                                                                                             dc.hi_gf);
+        k_ntt_coset_scale<<<dim3((unsigned)(((1ull << logn) + 255) / 256), nb ? nb : 1), 256, 0, ctx->stream>>>(
+            d, logn, dc.lo_g, dc.hi_gf, vstr);
         ZK_HIP(hipGetLastError());
       }
-      ZK_TRY(ntt_raw(ctx, d, logn, 0, false));
-      return ntt_bitrev(ctx, d, logn);
+      ZK_TRY(ntt_raw_epi_n(ctx, d, logn, 0, false, 0, nullptr, nullptr, nb, vstr));
+      return ntt_bitrev_scaled(ctx, d, logn, BitrevScale{0, nullptr, nullptr, nullptr}, nb, vstr);
     }
-    ZK_TRY(ntt_raw(ctx, d, logn, 1, false));
+    ZK_TRY(ntt_raw_epi_n(ctx, d, logn, 1, false, 0, nullptr, nullptr, nb, vstr));
     BitrevScale sc = coset ? BitrevScale{2, nullptr, dc.lo_gi, dc.hi_gi} : BitrevScale{1, dc.ninv_m, nullptr, nullptr};
-    return ntt_bitrev_scaled(ctx, d, logn, sc);
+    return ntt_bitrev_scaled(ctx, d, logn, sc, nb, vstr);
   }
   const uint32_t* tw;
   ZK_TRY(get_twiddles(ctx, logn, inverse, &tw));
   uint32_t* s;
-  ZK_TRY(ctx->ws.get("ntt_scratch", ((size_t)1 << logn) * 32, (void**)&s));
+  const size_t vw = ((size_t)1 << logn) * 8;  // words of a packed vector
+  ZK_TRY(ctx->ws.get("ntt_scratch", (nb ? nb : 1) * vw * 4, (void**)&s));
   hipStream_t st = ctx->stream;
   const std::vector<uint32_t> ks = ntt_groups(logn);
   const int ng = (int)ks.size();
@@ -752,15 +798,16 @@ int ntt_device(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inverse, int coset
   for (int g = 0; g < ng; g++) {
     ScopedKernelTimer tm(ctx, "ntt_group");
     const uint32_t* src = g == 0 ? d : s;
+    const NttBatch in{g == 0 ? vstr : vw, vw}, out{g == 0 ? vstr : vw, vstr};  // (src, dst) vector strides
     if (g < ng - 1) {
-      if (g == 0 && coset && !inverse) launch_group<false, 1, 0, false>(st, src, s, tw, logn, a, ks[g], pro);
-      else launch_group<false, 0, 0, false>(st, src, s, tw, logn, a, ks[g], pro);
+      if (g == 0 && coset && !inverse) launch_group<false, 1, 0, false>(st, src, s, tw, logn, a, ks[g], pro, nb, in);
+      else launch_group<false, 0, 0, false>(st, src, s, tw, logn, a, ks[g], pro, nb, in);
     } else if (!inverse) {
-      launch_group<false, 0, 0, true>(st, src, d, tw, logn, a, ks[g], epi);
+      launch_group<false, 0, 0, true>(st, src, d, tw, logn, a, ks[g], epi, nb, out);
     } else if (coset) {
-      launch_group<false, 0, 2, true>(st, src, d, tw, logn, a, ks[g], epi);
+      launch_group<false, 0, 2, true>(st, src, d, tw, logn, a, ks[g], epi, nb, out);
     } else {
-      launch_group<false, 0, 1, true>(st, src, d, tw, logn, a, ks[g], epi);
+      launch_group<false, 0, 1, true>(st, src, d, tw, logn, a, ks[g], epi, nb, out);
     }
     a -= ks[g];
   }

@@ -387,6 +387,31 @@ int zkmi_msm_submit_shared(zkmi_ctx* ctx, const zkmi_bases* const* bs, int k, si
   }
   return msm_submit_shared(ctx, bs, k, offset, d_scalars, n, jobs);
 }
+int zkmi_msm_batch_submit(zkmi_ctx* ctx, const zkmi_bases* b, size_t offset, const void* d_scalars, size_t n,
+                          size_t nb, size_t stride, zkmi_msm_job** job) {
+  ZK_DEVICE_GUARD(ctx);
+  if (!ctx || !b || !job) {
+    set_error("zkmi_msm_batch_submit: null argument");
+    return ZKMI_EINVAL;
+  }
+  return msm_batch_submit_shared(ctx, &b, 1, offset, d_scalars, n, nb, stride, job);
+}
+int zkmi_msm_batch_wait(zkmi_msm_job* job, uint64_t* out, size_t nb) {
+  if (job && nb && !out) {
+    set_error("zkmi_msm_batch_wait: null output");
+    return ZKMI_EINVAL;
+  }
+  return msm_batch_wait(job, out, nb);
+}
+int zkmi_ctx_set_batch_group(zkmi_ctx* ctx, int g) {
+  if (!ctx || g < 0 || g > 64) {
+    set_error("zkmi_ctx_set_batch_group: group must be 0 (automatic) or in [1, 64]");
+    return ZKMI_EINVAL;
+  }
+  ctx->batch_group = g;
+  return 0;
+}
+int zkmi_ctx_get_batch_group(const zkmi_ctx* ctx) { return ctx ? ctx->batch_group : -1; }
 int zkmi_msm_set_lanes(zkmi_ctx* ctx, int lanes) {
   if (!ctx || lanes < 1 || lanes > 8) {
     set_error("zkmi_msm_set_lanes: lanes must be in [1, 8]");
@@ -419,6 +444,18 @@ int zkmi_g2_add(const uint64_t a[16], const uint64_t b[16], uint64_t out[16]) {
 int zkmi_ntt_device(zkmi_ctx* ctx, void* d_data, uint32_t log_n, int inverse, int coset) {
   ZK_DEVICE_GUARD(ctx);
   ZK_TRY(ntt_device(ctx, (uint32_t*)d_data, log_n, inverse, coset));
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  return timer_flush(ctx);
+}
+int zkmi_ntt_batch_device(zkmi_ctx* ctx, void* d_data, uint32_t log_n, size_t nb, size_t stride, int inverse,
+                          int coset) {
+  ZK_DEVICE_GUARD(ctx);
+  if (!ctx || log_n > 28 || stride < ((size_t)32 << log_n) || (stride & 31) || nb > 65535 || (nb && !d_data)) {
+    set_error("zkmi_ntt_batch_device: log_n <= 28, nb <= 65535, stride a multiple of 32 and >= 2^log_n * 32");
+    return ZKMI_EINVAL;
+  }
+  if (nb == 0) return 0;
+  ZK_TRY(ntt_device_n(ctx, (uint32_t*)d_data, log_n, inverse, coset, (unsigned)nb, stride / 4));
   ZK_HIP(hipStreamSynchronize(ctx->stream));
   return timer_flush(ctx);
 }

@@ -80,6 +80,7 @@ struct zkmi_ctx {
   int msm_window = 0;  // 0 = auto
   int num_cus = 256;
   int msm_lanes = 2;  // concurrent MSM streams
+  int batch_group = 0;  // proofs / MSMs per batched launch sequence (0 = automatic)
   int lane_next = 0;
   std::vector<zk::MsmLane*> lanes;
   // set: MSM lanes wait on this event (recorded earlier on `stream`) instead
@@ -233,6 +234,12 @@ int msm_wait(zkmi_msm_job* job, uint64_t* out_affine);
 // plans agree); jobs[i] receives the job of bs[i]
 int msm_submit_shared(zkmi_ctx* ctx, const zkmi_bases* const* bs, int k, size_t offset, const void* d_scalars,
                       size_t n, zkmi_msm_job** jobs);
+// nb MSMs over one range of each of k base sets, vector i at d_scalars + i *
+// stride bytes: groups of vectors run as one launch sequence each (msm.hip);
+// jobs[i] is the batch job of bs[i] (finish it with msm_batch_wait)
+int msm_batch_submit_shared(zkmi_ctx* ctx, const zkmi_bases* const* bs, int k, size_t offset, const void* d_scalars,
+                            size_t n, size_t nb, size_t stride, zkmi_msm_job** jobs);
+int msm_batch_wait(zkmi_msm_job* job, uint64_t* out, size_t nb);
 void msm_job_free(zkmi_msm_job* job);
 int bases_upload(zkmi_ctx* ctx, int g2, const uint64_t* host_affine, size_t n, zkmi_bases** out);
 // convert canonical affine already in device memory (n points) into a bases set
@@ -254,6 +261,9 @@ int scalars_generate(zkmi_ctx* ctx, uint64_t seed, size_t first, size_t n, void*
 
 // NTT entry (ntt.hip): in-place on device, natural order
 int ntt_device(zkmi_ctx* ctx, uint32_t* d_data, uint32_t log_n, int inverse, int coset);
+// nb >= 1 vectors, vstr u32 words apart, in one launch sequence (nb = 0: the
+// single-vector launches of ntt_device)
+int ntt_device_n(zkmi_ctx* ctx, uint32_t* d_data, uint32_t log_n, int inverse, int coset, unsigned nb, size_t vstr);
 // per-log_n NTT domain tables (Montgomery): g^x = lo[x mod 2^KB] * hi[x >> KB]
 constexpr uint32_t COSET_KB = 14;
 struct DomainCache {

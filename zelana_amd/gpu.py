@@ -157,6 +157,13 @@ class Context:
     def set_window(self, c: int):
         check(lib().zkmi_msm_set_window(self.h, c))
 
+    def set_batch_group(self, g: int):
+        """Proofs / MSMs per batched launch sequence (0 = automatic, 1..64)."""
+        check(lib().zkmi_ctx_set_batch_group(self.h, g), "zkmi_ctx_set_batch_group")
+
+    def batch_group(self) -> int:
+        return lib().zkmi_ctx_get_batch_group(self.h)
+
     def set_lanes(self, lanes: int):
         """MSM lanes (capped at 2 while a communicator exists: stream budget)."""
         check(lib().zkmi_msm_set_lanes(self.h, lanes))
@@ -247,6 +254,24 @@ class Context:
         check(f(self.h, bases.h, offset, dscalars.ptr, n, _p64(out)), "zkmi_msm_device")
         return out
 
+    def msm_batch_submit(self, bases: Bases, dscalars: DeviceBuffer, n: int, nb: int, stride: int, offset: int = 0):
+        """Queue nb MSMs over one base set (vector i = n scalars at dscalars +
+        i * stride bytes); finish with msm_batch_wait."""
+        job = vp()
+        check(lib().zkmi_msm_batch_submit(self.h, bases.h, offset, dscalars.ptr, n, nb, stride, ctypes.byref(job)),
+              "zkmi_msm_batch_submit")
+        return (job, bases.g2, nb)
+
+    def msm_batch_wait(self, job):
+        h, g2, nb = job
+        out = np.zeros((nb, 16 if g2 else 8), np.uint64)
+        check(lib().zkmi_msm_batch_wait(h, _p64(out), nb), "zkmi_msm_batch_wait")
+        return out
+
+    def msm_batch(self, bases: Bases, dscalars: DeviceBuffer, n: int, nb: int, stride: int, offset: int = 0):
+        """(nb, 8 or 16) canonical affine results of nb MSMs over one base set."""
+        return self.msm_batch_wait(self.msm_batch_submit(bases, dscalars, n, nb, stride, offset))
+
     # --- NTT
     def ntt(self, data: np.ndarray, log_n: int, inverse=False, coset=False):
         d = np.ascontiguousarray(data, dtype=np.uint64).copy()
@@ -256,6 +281,11 @@ class Context:
 
     def ntt_device(self, buf: DeviceBuffer, log_n: int, inverse=False, coset=False):
         check(lib().zkmi_ntt_device(self.h, buf.ptr, log_n, int(inverse), int(coset)), "zkmi_ntt_device")
+
+    def ntt_batch_device(self, buf: DeviceBuffer, log_n: int, nb: int, stride: int, inverse=False, coset=False):
+        """nb in-place transforms, vector i at buf + i * stride bytes."""
+        check(lib().zkmi_ntt_batch_device(self.h, buf.ptr, log_n, nb, stride, int(inverse), int(coset)),
+              "zkmi_ntt_batch_device")
 
 
 def shard_range(total: int, nranks: int, rank: int):
@@ -586,3 +616,33 @@ def groth16_prove_resident(ctx: Context, pk: "ProvingKey", r1cs: R1CSDevice, dz:
     check(lib().zkmi_groth16_prove_resident(ctx.h, pk.h, r1cs.h, dz.ptr, _p64(_limbs(r)), _p64(_limbs(s)), _p64(a),
                                             _p64(b), _p64(c)), "zkmi_groth16_prove_resident")
     return a, b, c
+
+
+def _limbs_many(xs) -> np.ndarray:
+    return np.array([_limbs(int(x)) for x in xs], np.uint64).reshape(-1, 4)
+
+
+def groth16_prove_many_submit(ctx: Context, pk: "ProvingKey", r1cs: R1CSDevice, dz: DeviceBuffer, nb: int,
+                              stride: int, rs, ss):
+    """Queue nb resident proofs of same-shape witnesses (assignment i at dz +
+    i * stride bytes, blinding rs[i], ss[i]); finish with groth16_prove_many_wait."""
+    assert len(rs) == nb and len(ss) == nb
+    job = vp()
+    rr, sv = _limbs_many(rs), _limbs_many(ss)
+    check(lib().zkmi_groth16_prove_many_submit(ctx.h, pk.h, r1cs.h, dz.ptr, nb, stride, _p64(rr), _p64(sv),
+                                               ctypes.byref(job)), "zkmi_groth16_prove_many_submit")
+    return (job, nb)
+
+
+def groth16_prove_many_wait(job):
+    """[(A[8], B[16], C[8])] in submission order."""
+    h, nb = job
+    a, b, c = np.zeros((nb, 8), np.uint64), np.zeros((nb, 16), np.uint64), np.zeros((nb, 8), np.uint64)
+    check(lib().zkmi_groth16_prove_many_wait(h, nb, _p64(a), _p64(b), _p64(c)), "zkmi_groth16_prove_many_wait")
+    return [(a[i], b[i], c[i]) for i in range(nb)]
+
+
+def groth16_prove_many(ctx: Context, pk: "ProvingKey", r1cs: R1CSDevice, dz: DeviceBuffer, nb: int, stride: int,
+                       rs, ss):
+    return groth16_prove_many_wait(groth16_prove_many_submit(ctx, pk, r1cs, dz, nb, stride, rs, ss))
+

@@ -128,6 +128,7 @@ class Groth16Prover:
         # z buffer (zp::Groth16Prover::prove's scheme; the C++ synthesizer
         # records the program), used when the default synthesizer is
         self._shapes: dict = {}
+        self._many_z: dict = {}  # per shape: the strided z buffer of prove_many
 
     @classmethod
     def from_bytes(cls, pk_bytes: bytes, vk_bytes: bytes, device: int = 0, circuit=None, compressed=True,
@@ -205,6 +206,52 @@ class Groth16Prover:
         a, b, c = gpu.groth16_prove_resident(self.ctx, self.pk, dev, dz, r, s)
         return BatchProof(inputs, self.proof_to_solana_bytes(a, b, c),
                           int((time.perf_counter() - start) * 1000), a, b, c)
+
+    def prove_many(self, batches) -> list:
+        """Proofs of a list of (inputs, witness), in input order, each equal to
+        prove() on that item.  Items are grouped by circuit shape; a shape seen
+        for the first time is recorded by one ordinary prove(), the rest of its
+        group runs the shape's witness program once (run_many, a strided z
+        buffer) and one batched proof call (zkmi_groth16_prove_many), with r, s
+        from StdRng::seed_from_u64(batch_id) per item.  A custom `circuit`
+        synthesizer is proved item by item."""
+        batches = list(batches)
+        if self.circuit is not _native_synthesizer():
+            out = []
+            for inputs, witness in batches:
+                cs, z = self.circuit(inputs, witness)
+                out.append(self.prove_r1cs(cs, z, inputs))
+            return out
+        from . import host_prover as H
+        out: list = [None] * len(batches)
+        groups: dict = {}
+        for idx, (inputs, witness) in enumerate(batches):
+            groups.setdefault(H.l2_shape_key(inputs, witness), []).append(idx)
+        for key, idxs in groups.items():
+            if key not in self._shapes:  # records the shape (program, resident R1CS)
+                out[idxs[0]] = self.prove(*batches[idxs[0]])
+                idxs = idxs[1:]
+            if not idxs:
+                continue
+            start = time.perf_counter()
+            plan, wp, dev, _ = self._shapes[key]
+            nb, stride = len(idxs), plan.num_vars * 32
+            dzm = self._many_z.get(key)
+            if dzm is None or dzm.nbytes < nb * stride:
+                if len(self._many_z) >= 8:
+                    self._many_z.pop(next(iter(self._many_z)))
+                dzm = self._many_z[key] = gpu.DeviceBuffer(self.ctx, nb * stride)
+            rs, ss = [], []
+            for i in idxs:
+                rng = StdRng.seed_from_u64(batches[i][0].batch_id)
+                rs.append(rng.fr_rand())
+                ss.append(rng.fr_rand())
+            wp.run_many([H.l2_witness_inputs(*batches[i]) for i in idxs], dzm, stride)
+            proofs = gpu.groth16_prove_many(self.ctx, self.pk, dev, dzm, nb, stride, rs, ss)
+            ms = int((time.perf_counter() - start) * 1000 / nb)
+            for i, (a, b, c) in zip(idxs, proofs):
+                out[i] = BatchProof(batches[i][0], self.proof_to_solana_bytes(a, b, c), ms, a, b, c)
+        return out
 
     def prove_r1cs(self, cs, z, inputs: BatchPublicInputs) -> BatchProof:
         start = time.perf_counter()
