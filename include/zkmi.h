@@ -329,6 +329,37 @@ int zkmi_groth16_prove_many_wait(zkmi_proof_job* job, size_t nb, uint64_t* a_out
 int zkmi_groth16_prove_many(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_dev* cs, const void* d_z, size_t nb,
                             size_t z_stride, const uint64_t* r, const uint64_t* s, uint64_t* a_out, uint64_t* b_out,
                             uint64_t* c_out);
+/* R1CS satisfaction of assignments resident in HBM (arkworks
+ * ConstraintSystem::is_satisfied / which_is_unsatisfied; the reference proves
+ * in release mode, where nothing checks the witness).  What is checked are
+ * the rows: <a_i,z> <b_i,z> = <c_i,z> mod r for every i < num_constraints.
+ * z[0] = 1 and z < r remain the caller's contract. */
+#define ZKMI_ROW_NONE UINT64_MAX
+typedef struct {
+  uint64_t first_row;          /* lowest i with <a_i,z><b_i,z> != <c_i,z>; ZKMI_ROW_NONE if every row holds */
+  uint64_t n_bad;              /* number of such rows */
+  uint64_t a[4], b[4], c[4];   /* canonical <a_i,z>, <b_i,z>, <c_i,z> at first_row; zero if none */
+} zkmi_r1cs_status;
+/* nb assignments (z_i at d_z + i * z_stride, the prove_many layout: z_stride
+ * >= n_vars * 32, a multiple of 32) against a resident R1CS; synchronous.
+ * Runs the witness map's mat-vecs (no transform) in chunks of assignments
+ * (zkmi_ctx_set_batch_group, or automatic: a bounded workspace) and one scan
+ * over their outputs.  out: nb statuses; nb = 0 is valid. */
+int zkmi_r1cs_check(zkmi_ctx* ctx, const zkmi_r1cs_dev* cs, const void* d_z, size_t nb, size_t z_stride,
+                    zkmi_r1cs_status* out);
+/* Proof jobs submitted while on also check their witness: the scan runs on
+ * the witness map's mat-vec outputs, before the transforms overwrite them.
+ * Off by default; off, no kernel or copy is added.  Proofs are the same bytes
+ * either way, and a wait returns the proof and ZKMI_OK whether or not the
+ * witness is satisfied (the reference's semantics): the status is
+ * information, not an error.  A job keeps the setting it was submitted
+ * with. */
+int zkmi_ctx_set_prove_check(zkmi_ctx* ctx, int on);
+int zkmi_ctx_get_prove_check(const zkmi_ctx* ctx);
+/* statuses of the proofs of the proof job most recently WAITED on this
+ * context, in proof order; *count = 0 if that job was submitted with the
+ * check off; ZKMI_EINVAL if cap < count (*count is still set) */
+int zkmi_groth16_last_check(zkmi_ctx* ctx, zkmi_r1cs_status* out, size_t cap, size_t* count);
 /* Benchmark helper: a random proving key of domain 2^log_n with the given
  * instance/witness counts, generated in HBM.  Proofs made with it do not
  * verify; the proving work is identical to a real key of that shape. */

@@ -5,6 +5,7 @@ against the loops a caller has without it.  Prints one JSON line.
     python tools/prove_many.py product           # prove_many, nb = 1 .. 64, raw and end to end
     python tools/prove_many.py sweep [lo hi]     # synthetic keys 2^lo .. 2^hi: batched against pipelined
     python tools/prove_many.py groups            # product shape: group size 4 .. 64 at nb = 16 and 64
+    python tools/prove_many.py --check [big]     # the R1CS check: off (also on an older library), on, stand-alone
 
 `baseline` uses only entry points older than prove_many, so it also runs on
 an older libzkmi.so (ZKMI_LIB=...): build the commit to compare against and
@@ -159,6 +160,73 @@ def leg_sweep(lo, hi):
     return out
 
 
+def leg_check(big):
+    """Product shape: the single resident proof and prove_many at nb = 1 and 64
+    with the prove check off (these entry points exist in an older libzkmi.so
+    too: ZKMI_LIB=...), then on, and the stand-alone zkmi_r1cs_check.  big: also
+    one large proof (2^17 synthetic key) off and on, and the stand-alone check
+    of the 2^21 zelana_batch shape (batch 70) beside the download of its z."""
+    from zelana_amd import gpu
+    from zelana_amd._lib import lib
+    ctx, pk, vk, dev, z, r, s, _ = product_setup()
+    stride = z.nbytes
+    dz = gpu.DeviceBuffer(ctx, 64 * stride)
+    dz.upload(np.tile(z.reshape(1, -1), (64, 1)))
+    has = hasattr(lib(), "zkmi_r1cs_check")
+
+    def point(fn1, fnm):
+        row = {"resident_ms": timed(fn1, 1)}
+        for nb in (1, 64):
+            row[f"many_nb{nb}_ms"] = timed(lambda: fnm(nb), nb)
+        row["proofs"] = sorted({digest(fn1())} | {digest(p) for nb in (1, 64) for p in fnm(nb)})
+        return row
+
+    fn1 = lambda: gpu.groth16_prove_resident(ctx, pk, dev, dz.view(0, stride), r, s)
+    fnm = lambda nb: gpu.groth16_prove_many(ctx, pk, dev, dz, nb, stride, [r] * nb, [s] * nb)
+    out = {"has_check": has, "off": point(fn1, fnm)}
+    if has:
+        ctx.set_prove_check(True)
+        out["on"] = point(fn1, fnm)
+        st = gpu.groth16_last_check(ctx)
+        out["on"]["statuses"] = len(st)
+        out["on"]["first_row"], out["on"]["n_bad"] = st[0].first_row, st[0].n_bad
+        ctx.set_prove_check(False)
+        out["same_proofs"] = out["on"]["proofs"] == out["off"]["proofs"]
+        for nb in (1, 64):
+            out[f"standalone_nb{nb}_ms"] = timed(lambda: gpu.r1cs_check(ctx, dev, dz, nb, stride), nb)
+    if big:
+        from zelana_amd.r1cs import synthetic_fast
+        m = (1 << 17) - 8
+        cs2, z2 = synthetic_fast(m, 4, m, seed=17)
+        pk2 = gpu.synthetic_pk(ctx, 87, 17, 4, m)
+        pk2.precompute()
+        dev2 = gpu.R1CSDevice(ctx, cs2)
+        dz2 = gpu.DeviceBuffer(ctx, z2.nbytes)
+        dz2.upload(z2)
+        big1 = lambda: gpu.groth16_prove_resident(ctx, pk2, dev2, dz2, 3, 4)
+        out["big17_off_ms"] = timed(big1, 1)
+        if has:
+            ctx.set_prove_check(True)
+            out["big17_on_ms"] = timed(big1, 1)
+            ctx.set_prove_check(False)
+            out["big17_standalone_ms"] = timed(lambda: gpu.r1cs_check(ctx, dev2, dz2), 1)
+        for o in (dz2, dev2, pk2):
+            (o.free if hasattr(o, "free") else o.close)()
+        if has:
+            from zelana_amd import zbatch
+            d = zbatch.load_prover_toml(os.path.join(ROOT, "tests", "golden", "zelana_batch_70_Prover.toml"))
+            cs3, z3, _ = zbatch.build(d)
+            dev3 = gpu.R1CSDevice(ctx, cs3)
+            dz3 = gpu.DeviceBuffer(ctx, z3.nbytes)
+            dz3.upload(z3)
+            st3 = gpu.r1cs_check(ctx, dev3, dz3)[0]
+            out["batch70"] = {"m": cs3.num_constraints, "z_mb": round(z3.nbytes / 2**20, 1),
+                              "first_row": st3.first_row, "n_bad": st3.n_bad,
+                              "standalone_ms": timed(lambda: gpu.r1cs_check(ctx, dev3, dz3), 1),
+                              "download_z_ms": timed(lambda: dz3.download(np.empty_like(z3)), 1)}
+    return out
+
+
 def main():
     leg = sys.argv[1] if len(sys.argv) > 1 else "product"
     if leg == "baseline":
@@ -167,6 +235,8 @@ def main():
         res = leg_product()
     elif leg == "groups":
         res = leg_groups()
+    elif leg in ("check", "--check"):
+        res = leg_check(len(sys.argv) > 2 and sys.argv[2] == "big")
     elif leg == "sweep":
         res = leg_sweep(int(sys.argv[2]) if len(sys.argv) > 2 else 10, int(sys.argv[3]) if len(sys.argv) > 3 else 18)
     else:

@@ -40,6 +40,15 @@ class R1CSStruct(ctypes.Structure):
     ]
 
 
+class R1CSStatusStruct(ctypes.Structure):
+    """zkmi_r1cs_status"""
+    _fields_ = [("first_row", ctypes.c_uint64), ("n_bad", ctypes.c_uint64), ("a", ctypes.c_uint64 * 4),
+                ("b", ctypes.c_uint64 * 4), ("c", ctypes.c_uint64 * 4)]
+
+
+ROW_NONE = 2**64 - 1  # ZKMI_ROW_NONE
+
+
 # (name, restype, argtypes) — every symbol declared in include/zkmi.h
 SIGNATURES = [
     ("zkmi_last_error", ctypes.c_char_p, []),
@@ -113,6 +122,10 @@ SIGNATURES = [
     ("zkmi_groth16_prove_many_submit", ctypes.c_int, [vp, vp, vp, vp, sz, sz, u64p, u64p, ctypes.POINTER(vp)]),
     ("zkmi_groth16_prove_many_wait", ctypes.c_int, [vp, sz, u64p, u64p, u64p]),
     ("zkmi_groth16_prove_many", ctypes.c_int, [vp, vp, vp, vp, sz, sz, u64p, u64p, u64p, u64p, u64p]),
+    ("zkmi_r1cs_check", ctypes.c_int, [vp, vp, vp, sz, sz, ctypes.POINTER(R1CSStatusStruct)]),
+    ("zkmi_ctx_set_prove_check", ctypes.c_int, [vp, ctypes.c_int]),
+    ("zkmi_ctx_get_prove_check", ctypes.c_int, [vp]),
+    ("zkmi_groth16_last_check", ctypes.c_int, [vp, ctypes.POINTER(R1CSStatusStruct), sz, ctypes.POINTER(sz)]),
     ("zkmi_pk_synthetic", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint32, sz, sz, ctypes.POINTER(vp)]),
     ("zkmi_groth16_setup", ctypes.c_int, [vp, vp, u64p, u64p, u64p, ctypes.POINTER(vp)]),
     ("zkmi_pk_serialize", ctypes.c_int, [vp, u8p, sz, ctypes.POINTER(sz)]),

@@ -73,17 +73,22 @@ class ZBatchProver:
     counts and tree depth are constants of main.nr, so every batch of the
     circuit has the same shape).  pk: a gpu.ProvingKey for this R1CS; if None,
     circuit_specific_setup runs on the GPU with StdRng::seed_from_u64(keygen_seed).
-    shape: zbatch.build's slot counts / depth (reduced circuits in tests)."""
+    shape: zbatch.build's slot counts / depth (reduced circuits in tests).
+    check: check every batch's witness against the R1CS on the GPU, inside the
+    proof; generate_batch_proof then raises ValueError for an unsatisfied
+    batch (its result goes to settlement, where such a proof is rejected)."""
 
     def __init__(self, ctx: gpu.Context, template: dict, pk: gpu.ProvingKey | None = None, keygen_seed: int = 0,
-                 precompute: bool = True, **shape):
+                 precompute: bool = True, check: bool = False, **shape):
         from . import wprog
         from .keygen import circuit_specific_setup
 
         self.ctx = ctx
+        self.check = check
         self.shape = shape
         cs, z, _ = zbatch.build(template, **shape)
         self.num_instance = cs.num_instance
+        self.num_constraints = cs.num_constraints
         self.vk = None
         if pk is None:
             pk, self.vk = circuit_specific_setup(ctx, cs, StdRng.seed_from_u64(keygen_seed))
@@ -102,7 +107,19 @@ class ZBatchProver:
         self.wp.run(zbatch.batch_inputs(batch, **self.shape), self.dz)
         rng = StdRng.seed_from_u64(int(zbatch._f(batch.get("batch_id", 0))))
         r, s = rng.fr_rand(), rng.fr_rand()
-        a, b, c = gpu.groth16_prove_resident(self.ctx, self.pk, self.dev, self.dz, r, s)
+        if not self.check:
+            a, b, c = gpu.groth16_prove_resident(self.ctx, self.pk, self.dev, self.dz, r, s)
+        else:
+            prev = self.ctx.prove_check()
+            self.ctx.set_prove_check(True)
+            try:
+                a, b, c = gpu.groth16_prove_resident(self.ctx, self.pk, self.dev, self.dz, r, s)
+            finally:
+                self.ctx.set_prove_check(prev)
+            st = gpu.groth16_last_check(self.ctx)[0]
+            if st.first_row is not None:
+                raise ValueError(f"zelana_batch witness does not satisfy the circuit: constraint {st.first_row} "
+                                 f"fails first, {st.n_bad} of {self.num_constraints} fail")
         proof_bytes = gpu.proof_to_solana_bytes(a, b, c)
         # the public inputs the proof binds: z slots 1..num_instance of the
         # witness the GPU proved (not the batch dict, which a caller could

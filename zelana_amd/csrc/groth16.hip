@@ -19,6 +19,7 @@
 
 #include "dev_io.h"
 #include "ec.h"
+#include "r1cs_row.h"
 #include "zkmi_internal.h"
 
 struct zkmi_pk {
@@ -339,6 +340,58 @@ __global__ void __launch_bounds__(256) k_matvec(const RP* __restrict__ rowptr, c
   for (int d = g >> 1; d >= 1; d >>= 1) part = add<FrP>(part, fe_shfl_xor(part, d));  // every lane shuffles
   if (j < nlong && gl == 0) st_fe(out + (size_t)row * 8, part);
 }
+// ------------------------------------------------------------ R1CS check
+// Satisfaction of the rows from the mat-vec outputs (value form, < 2r), before
+// the transforms overwrite them.  Status block per assignment, the layout of
+// zkmi_r1cs_status: first_row, n_bad, then a, b, c at first_row (3 x 4 u64).
+constexpr unsigned CHK_U64 = sizeof(zkmi_r1cs_status) / 8;
+static_assert(sizeof(zkmi_r1cs_status) == 14 * 8, "status block layout");
+__global__ void __launch_bounds__(256) k_r1cs_status_init(unsigned long long* __restrict__ st, unsigned cnt) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < cnt) st[i] = i % CHK_U64 == 0 ? ~0ull : 0ull;
+}
+// One lane per row i < m (rows m <= i < n hold A's input copies or zero and
+// are not read); blockIdx.y is the assignment, its vectors vstr words after
+// the one before.  A wave's bad rows are one ballot; the block's four waves
+// meet in LDS, and only a block with a bad row touches the status: one
+// atomicMin on first_row and one atomicAdd on n_bad.
+__global__ void __launch_bounds__(256) k_r1cs_scan(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                   const uint32_t* __restrict__ c, size_t m, size_t vstr,
+                                                   unsigned long long* __restrict__ st) {
+  __shared__ uint32_t s_cnt[4], s_first[4];
+  const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
+  const size_t off = (size_t)blockIdx.y * vstr + i * 8;
+  bool bad = false;
+  if (i < m) bad = r1cs_row_bad(ld_fe(a + off), ld_fe(b + off), ld_fe(c + off));
+  const unsigned long long mask = __ballot(bad);
+  const unsigned wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    s_cnt[wave] = (uint32_t)__popcll(mask);
+    s_first[wave] = mask ? wave * 64 + (uint32_t)(__ffsll(mask) - 1) : 256u;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const uint32_t cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+  if (!cnt) return;
+  const uint32_t first = min(min(s_first[0], s_first[1]), min(s_first[2], s_first[3]));
+  st += (size_t)blockIdx.y * CHK_U64;
+  atomicMin(st, (unsigned long long)blockIdx.x * 256 + first);
+  atomicAdd(st + 1, (unsigned long long)cnt);
+}
+// canonical a, b, c of each assignment's first bad row (one block per
+// assignment, lanes 0..2 take one value each), after the scan
+__global__ void __launch_bounds__(64) k_r1cs_values(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                    const uint32_t* __restrict__ c, size_t vstr,
+                                                    unsigned long long* __restrict__ st) {
+  st += (size_t)blockIdx.x * CHK_U64;
+  const unsigned long long row = st[0];
+  const unsigned t = threadIdx.x;
+  if (row == ~0ull || t >= 3) return;
+  const uint32_t* v = (t == 0 ? a : t == 1 ? b : c) + (size_t)blockIdx.x * vstr + (size_t)row * 8;
+  uint32_t w[8];
+  pack(w, reduce<FrP>(ld_fe(v)));
+  for (int k = 0; k < 4; k++) st[2 + 4 * t + k] = w[2 * k] | ((unsigned long long)w[2 * k + 1] << 32);
+}
 // powers table: tab[x] = c * base^(x * step) for x < cnt (Montgomery), runs of 64
 __global__ void __launch_bounds__(256) k_pow_table(uint32_t* __restrict__ tab, uint32_t cnt, const uint32_t* base_c,
                                                    uint64_t step, const uint32_t* mult_m) {
@@ -639,8 +692,41 @@ static uint32_t domain_log(size_t need) {
   return k;
 }
 
+// Queue the R1CS check of nb assignments on the context stream, right after
+// the mat-vecs that wrote a, b, c (assignment i's vectors i * vstr words on)
+// and before anything overwrites them: the status reset, the scan, the first
+// bad row's values (a second one-block-per-assignment launch), and the copy of
+// the nb statuses to `host`.  The device slot is shared by every check of the
+// context (stream order keeps proofs in flight apart); `host` belongs to the
+// caller.  done: recorded after the copy when given.
+static int r1cs_scan_queue(zkmi_ctx* ctx, const uint32_t* a, const uint32_t* b, const uint32_t* c, size_t m,
+                           size_t vstr, unsigned nb, zkmi_r1cs_status* host, hipEvent_t done) {
+  hipStream_t st = ctx->stream;
+  unsigned long long* d_st;
+  ZK_TRY(ctx->ws.get("g16_chk", (size_t)nb * sizeof(zkmi_r1cs_status), (void**)&d_st));
+  {
+    ScopedKernelTimer tm(ctx, "g16_check");
+    k_r1cs_status_init<<<(nb * CHK_U64 + 255) / 256, 256, 0, st>>>(d_st, nb * CHK_U64);
+    if (m) {
+      k_r1cs_scan<<<dim3((unsigned)((m + 255) / 256), nb), 256, 0, st>>>(a, b, c, m, vstr, d_st);
+      k_r1cs_values<<<nb, 64, 0, st>>>(a, b, c, vstr, d_st);
+    }
+    ZK_HIP(hipGetLastError());
+  }
+  ZK_HIP(hipMemcpyAsync(host, d_st, (size_t)nb * sizeof(zkmi_r1cs_status), hipMemcpyDeviceToHost, st));
+  if (done) ZK_HIP(hipEventRecord(done, st));
+  return 0;
+}
+// a proof job's request for the check: where its statuses go (pinned, owned by
+// the job) and the event that covers the copy
+struct ChkReq {
+  zkmi_r1cs_status* host;
+  hipEvent_t done;
+};
+
 // h (bit-reversed layout, canonical, n elements) into d_h from device z
-static int witness_map_dev(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, uint32_t logn, uint32_t* d_h) {
+static int witness_map_dev(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, uint32_t logn, uint32_t* d_h,
+                           const ChkReq* chk = nullptr) {
   hipStream_t st = ctx->stream;
   size_t m = dr.m, l = dr.l, nv = l + dr.w;
   size_t n = (size_t)1 << logn;
@@ -673,6 +759,7 @@ static int witness_map_dev(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z
     }
     ZK_HIP(hipGetLastError());
   }
+  if (chk) ZK_TRY(r1cs_scan_queue(ctx, a, b, c, m, 0, 1, chk->host, chk->done));
   // evaluations -> coefficients (DIF, bit-reversed) -> * n^-1 g^i -> coset
   // evaluations (DIT, natural)
   uint32_t* vecs[3] = {a, b, c};
@@ -696,8 +783,36 @@ static int witness_map_dev(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z
 // b's, then the c's -- so each NTT direction is one batched launch sequence
 // over all 3 nb of them; h_i (bit-reversed layout, as witness_map_dev) ends up
 // in a_i = d_v + i * n elements.  ws: nb (3 n [+ nv]) x 32 B.
+// the batched mat-vecs of nb assignments into a, b, c (nb vectors of n
+// elements each; zm: nb x nv x 32 B for the legacy form, else unused).  is_a:
+// A's vectors also take the input copies in rows m .. m + l (the witness map);
+// n = m with is_a = 0 writes the rows alone (the stand-alone check).
+static int matvec_many(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, size_t zstr, unsigned nb, size_t n,
+                       int is_a, uint32_t* zm, uint32_t* a, uint32_t* b, uint32_t* c) {
+  hipStream_t st = ctx->stream;
+  const size_t m = dr.m, l = dr.l, nv = l + dr.w;
+  const bool legacy = !dr.dict[0] || !dr.dict[1] || !dr.dict[2];
+  const unsigned gn = (unsigned)((n + 255) / 256);
+  ScopedKernelTimer tm(ctx, "g16_matvec");
+  if (legacy) k_to_mont_fr<<<dim3((unsigned)((nv + 255) / 256), nb), 256, 0, st>>>(d_z, nv, zm, zstr);
+  uint32_t* outs[3] = {a, b, c};
+  for (int t = 0; t < 3; t++) {
+    const unsigned gl = (unsigned)(((size_t)dr.nlong[t] * dr.glong[t] + 255) / 256);
+    if (dr.dict[t])
+      k_matvec<true, uint32_t, true><<<dim3(gn + gl, nb), 256, 0, st>>>(
+          dr.rp32[t], nullptr, nullptr, dr.cv[t], dr.coef[t], zm, d_z, m, l, n, is_a && t == 0, dr.lrow[t],
+          dr.nlong[t], dr.glong[t], gn, outs[t], zstr, nv * 8);
+    else
+      k_matvec<false, uint64_t, true><<<dim3(gn + gl, nb), 256, 0, st>>>(
+          dr.rp[t], dr.col[t], dr.val[t], nullptr, nullptr, zm, d_z, m, l, n, is_a && t == 0, dr.lrow[t],
+          dr.nlong[t], dr.glong[t], gn, outs[t], zstr, nv * 8);
+  }
+  ZK_HIP(hipGetLastError());
+  return 0;
+}
+
 static int witness_map_many(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, size_t zstr, unsigned nb,
-                            uint32_t logn, uint32_t* d_v) {
+                            uint32_t logn, uint32_t* d_v, const ChkReq* chk = nullptr) {
   hipStream_t st = ctx->stream;
   size_t m = dr.m, l = dr.l, nv = l + dr.w;
   size_t n = (size_t)1 << logn;
@@ -709,23 +824,8 @@ static int witness_map_many(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_
   const size_t vw = n * 8;  // words per vector
   uint32_t *a = d_v, *b = d_v + (size_t)nb * vw, *c = d_v + 2 * (size_t)nb * vw;
   unsigned gn = (unsigned)((n + 255) / 256);
-  {
-    ScopedKernelTimer tm(ctx, "g16_matvec");
-    if (legacy) k_to_mont_fr<<<dim3((unsigned)((nv + 255) / 256), nb), 256, 0, st>>>(d_z, nv, zm, zstr);
-    uint32_t* outs[3] = {a, b, c};
-    for (int t = 0; t < 3; t++) {
-      const unsigned gl = (unsigned)(((size_t)dr.nlong[t] * dr.glong[t] + 255) / 256);
-      if (dr.dict[t])
-        k_matvec<true, uint32_t, true><<<dim3(gn + gl, nb), 256, 0, st>>>(
-            dr.rp32[t], nullptr, nullptr, dr.cv[t], dr.coef[t], zm, d_z, m, l, n, t == 0, dr.lrow[t], dr.nlong[t],
-            dr.glong[t], gn, outs[t], zstr, nv * 8);
-      else
-        k_matvec<false, uint64_t, true><<<dim3(gn + gl, nb), 256, 0, st>>>(
-            dr.rp[t], dr.col[t], dr.val[t], nullptr, nullptr, zm, d_z, m, l, n, t == 0, dr.lrow[t], dr.nlong[t],
-            dr.glong[t], gn, outs[t], zstr, nv * 8);
-    }
-    ZK_HIP(hipGetLastError());
-  }
+  ZK_TRY(matvec_many(ctx, dr, d_z, zstr, nb, n, 1, zm, a, b, c));
+  if (chk) ZK_TRY(r1cs_scan_queue(ctx, a, b, c, m, vw, nb, chk->host, chk->done));
   // as witness_map_dev, over all 3 nb vectors at once
   ZK_TRY(ntt_raw_epi_n(ctx, d_v, logn, 1, false, 2, dc.lo_g, dc.hi_g, 3 * nb, vw));
   ZK_TRY(ntt_raw_epi_n(ctx, d_v, logn, 0, true, 0, nullptr, nullptr, 3 * nb, vw));
@@ -737,6 +837,42 @@ static int witness_map_many(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_
   ZK_TRY(ntt_raw_epi_n(ctx, a, logn, 1, false, 2, dc.lo_gi, dc.hi_gi, nb, vw));
   ZK_HIP(hipGetLastError());
   return 0;
+}
+
+// Stand-alone check of nb resident assignments (zkmi_r1cs_check): the witness
+// map's mat-vecs with n = m and is_a = 0 (the rows alone) into workspace, then
+// the scan; no transform.  Chunks of G assignments keep the workspace bounded:
+// G = zkmi_ctx_set_batch_group, or as many as fit 96 MB of vectors (1..64).
+// Synchronous.
+int r1cs_check(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, size_t nb, size_t z_stride,
+               zkmi_r1cs_status* out) {
+  const size_t m = dr.m, nv = dr.l + dr.w;
+  if (z_stride < nv * 32 || (z_stride & 31)) {
+    set_error("r1cs_check: z_stride %zu must be a multiple of 32 and >= %zu", z_stride, nv * 32);
+    return ZKMI_EINVAL;
+  }
+  if (!nb) return 0;
+  const size_t zstr = z_stride / 4, vw = m * 8;
+  const bool legacy = !dr.dict[0] || !dr.dict[1] || !dr.dict[2];
+  size_t G = ctx->batch_group > 0 ? (size_t)ctx->batch_group
+                                  : std::min<size_t>(64, ((size_t)96 << 20) / std::max<size_t>(1, 3 * m * 32));
+  G = std::min(std::max<size_t>(G, 1), nb);
+  uint32_t *v = nullptr, *zm = nullptr;
+  if (m) ZK_TRY(ctx->ws.get("chk_v", 3 * G * m * 32, (void**)&v));
+  if (m && legacy) ZK_TRY(ctx->ws.get("chk_zm", G * nv * 32, (void**)&zm));
+  int rc = 0;
+  for (size_t b0 = 0; b0 < nb && !rc; b0 += G) {
+    const unsigned g = (unsigned)std::min(G, nb - b0);
+    uint32_t *a = v, *b = v + (size_t)g * vw, *c = v + 2 * (size_t)g * vw;
+    if (m) rc = matvec_many(ctx, dr, d_z + b0 * zstr, zstr, g, m, 0, zm, a, b, c);
+    if (!rc) rc = r1cs_scan_queue(ctx, a, b, c, m, vw, g, out + b0, nullptr);
+  }
+  // (also after a failure: a copy into `out` may be in flight)
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
+    set_error("r1cs_check: stream synchronisation failed");
+    rc = ZKMI_EHIP;
+  }
+  return rc ? rc : timer_flush(ctx);
 }
 
 static int check_cs(const zkmi_r1cs* cs) {
@@ -1063,9 +1199,41 @@ struct zkmi_proof_job {
   const zkmi_r1cs_dev* dr = nullptr;
   const uint32_t* dz = nullptr;
   size_t zstr = 0, next = 0;
+  // R1CS check: the context's setting sampled at submit (a many-job's later
+  // parts use it, not what the context holds by then).  A part's statuses
+  // (one, or gnb) land in chk, pinned memory of its own, once chk_done has
+  // passed; a many-job gathers its parts' in proof order.
+  bool check = false;
+  zkmi_r1cs_status* chk = nullptr;
+  hipEvent_t chk_done = nullptr;
 };
 
 namespace zk {
+
+// the pinned status buffer and event of a job submitted with the check on
+static int chk_acquire(zkmi_ctx* ctx, zkmi_proof_job* pj, size_t nb, ChkReq* req) {
+  pj->check = true;
+  ZK_HIP(hipEventCreateWithFlags(&pj->chk_done, hipEventDisableTiming));
+  ZK_TRY(ctx_pinned_get(ctx, nb * sizeof(zkmi_r1cs_status), (void**)&pj->chk));
+  req->host = pj->chk;
+  req->done = pj->chk_done;
+  return 0;
+}
+// (a copy into the buffer may be in flight: it goes back to the pool after it)
+static void chk_release(zkmi_proof_job* pj) {
+  if (pj->chk_done) {
+    (void)hipEventSynchronize(pj->chk_done);
+    hipEventDestroy(pj->chk_done);
+    pj->chk_done = nullptr;
+  }
+  if (pj->chk) ctx_pinned_put(pj->pk->ctx, pj->chk), pj->chk = nullptr;
+}
+// the job's nb statuses, once the event after their copy has passed
+static int chk_collect(zkmi_proof_job* pj, size_t nb, std::vector<zkmi_r1cs_status>* out) {
+  ZK_HIP(hipEventSynchronize(pj->chk_done));
+  if (out) out->insert(out->end(), pj->chk, pj->chk + nb);
+  return 0;
+}
 
 // ------------------------------------------------------------ prove
 // Small proofs (configs[0]: a 2^13 domain) are latency-bound: every kernel
@@ -1084,7 +1252,7 @@ namespace zk {
 // hardware queue (GPU_MAX_HW_QUEUES = 4 with the context stream), 2.05 ms.)
 constexpr size_t SMALL_PROOF_MAX = (size_t)1 << 16;  // domains up to which the small schedule applies
 static int prove_submit_small(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, const uint32_t* dz,
-                              uint32_t logn, uint32_t* dh, zkmi_msm_job** jobs) {
+                              uint32_t logn, uint32_t* dh, zkmi_msm_job** jobs, const ChkReq* chk) {
   const size_t l = dr.l, w = dr.w, nv = l + w, n = pk->n;
   const int nl = std::max(1, ctx->msm_lanes);
   if (!ctx->prove_fork) ZK_HIP(hipEventCreateWithFlags(&ctx->prove_fork, hipEventDisableTiming));
@@ -1095,7 +1263,7 @@ static int prove_submit_small(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& d
     ZK_HIP(hipGetLastError());
   }
   ZK_HIP(hipEventRecord(ctx->prove_fork, ctx->stream));
-  ZK_TRY(witness_map_dev(ctx, dr, dz, logn, dh));
+  ZK_TRY(witness_map_dev(ctx, dr, dz, logn, dh, chk));
   ctx->msm_fork = ctx->prove_fork;
   int rc = 0;
   // l first (lane 1 starts while the host still queues the long B chain)
@@ -1120,8 +1288,9 @@ static int prove_submit_small(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& d
 // core: R1CS and full assignment z already resident in HBM.  submit queues
 // everything (the witness map on the context stream, the MSMs on the lanes)
 // and returns; several proofs may be in flight, finished in order by wait.
+// check: also queue the R1CS check of z (its status comes back with the wait)
 int groth16_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, const uint32_t* dz,
-                         const uint64_t r[4], const uint64_t s[4], zkmi_proof_job** out) {
+                         const uint64_t r[4], const uint64_t s[4], bool check, zkmi_proof_job** out) {
   *out = nullptr;
   size_t l = dr.l, w = dr.w, nv = l + w;
   uint32_t logn = domain_log(dr.m + l);
@@ -1146,6 +1315,22 @@ int groth16_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, co
   zkmi_msm_job** jobs = pj->jobs;
   for (int i = 0; i < 5; i++) jobs[i] = nullptr;
   int rc = 0;
+  // The check's copy is queued on the context stream inside the witness map,
+  // so before the h MSM's lane forks from that stream (msm_submit with
+  // ctx->msm_fork == nullptr records the lane's fork event there): waiting for
+  // jobs[0] would order it.  An MSM over no points queues nothing, though (a
+  // domain of one element), so the job waits for an event of its own, recorded
+  // right after the copy.
+  ChkReq chk_req, *chk = nullptr;
+  if (check) {
+    rc = chk_acquire(ctx, pj, 1, &chk_req);
+    chk = &chk_req;
+  }
+  if (rc) {
+    chk_release(pj);
+    delete pj;
+    return rc;
+  }
 // 1: large-proof schedule below (measured, 2^22 L2 proofs 34.7-34.8 ->
 // 36.1-36.2/s, two in flight 35.5-35.9 -> 37.2-37.3/s; zelana_batch 81.3-81.6
 // -> 84.8-85.0/s).  0: the round-5 order (all MSMs, then the witness map).
@@ -1153,7 +1338,7 @@ int groth16_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, co
 #define ZK_G2_AFTER_WM 1
 #endif
   if (n <= SMALL_PROOF_MAX) {
-    rc = prove_submit_small(ctx, pk, dr, dz, logn, dh, jobs);
+    rc = prove_submit_small(ctx, pk, dr, dz, logn, dh, jobs, chk);
   } else if (ZK_G2_AFTER_WM && pk->d_bidx) {
     // The witness map's NTTs are the path to the h MSM.  Beside the G2
     // accumulation (248 VGPRs, 2 waves per SIMD) no NTT wave fits on a SIMD;
@@ -1170,7 +1355,7 @@ int groth16_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, co
       rc = hipGetLastError() == hipSuccess ? 0 : ZKMI_EHIP;
     }
     if (!rc) rc = hipEventRecord(ctx->prove_fork, ctx->stream) == hipSuccess ? 0 : ZKMI_EHIP;
-    if (!rc) rc = witness_map_dev(ctx, dr, dz, logn, dh);
+    if (!rc) rc = witness_map_dev(ctx, dr, dz, logn, dh, chk);
     if (!rc) rc = hipEventRecord(ctx->wm_done, ctx->stream) == hipSuccess ? 0 : ZKMI_EHIP;
     ctx->msm_fork = ctx->prove_fork;
     if (!rc) rc = msm_submit(ctx, pk->l_query, 0, dz + l * 8, w, &jobs[1]);
@@ -1199,12 +1384,13 @@ int groth16_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, co
     const zkmi_bases* abq[3] = {pk->a_query, pk->b_g1_query, pk->b_g2_query};
     rc = msm_submit_shared(ctx, abq, 3, 1, dz + 8, nv - 1, &jobs[2]);
   }
-  if (!rc) rc = witness_map_dev(ctx, dr, dz, logn, dh);
+  if (!rc) rc = witness_map_dev(ctx, dr, dz, logn, dh, chk);
   if (!rc) rc = msm_submit(ctx, pk->h_query_rev, 0, dh, n - 1, &jobs[0]);
   }
   if (rc) {
     for (auto* j : pj->jobs)
       if (j) msm_job_free(j);
+    chk_release(pj);
     delete pj;
     return rc;
   }
@@ -1214,7 +1400,9 @@ int groth16_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, co
   return 0;
 }
 
-int groth16_prove_wait(zkmi_proof_job* pj, uint64_t a_out[8], uint64_t b_out[16], uint64_t c_out[8]) {
+// chk_out: the job's status is appended when it was submitted with the check on
+int groth16_prove_wait(zkmi_proof_job* pj, uint64_t a_out[8], uint64_t b_out[16], uint64_t c_out[8],
+                       std::vector<zkmi_r1cs_status>* chk_out) {
   const zkmi_pk* pk = pj->pk;
   zkmi_msm_job** jobs = pj->jobs;
   uint64_t h_acc[8], l_acc[8], a_acc[8], b1_acc[8], b2_acc[16];
@@ -1235,6 +1423,8 @@ int groth16_prove_wait(zkmi_proof_job* pj, uint64_t a_out[8], uint64_t b_out[16]
     groth16_asm_c(l_acc, h_acc, &pj->asm_st, a_out, c_out);
     memcpy(b_out, b_tmp, sizeof(b_tmp));
   }
+  if (!rc && pj->check) rc = chk_collect(pj, 1, chk_out);
+  chk_release(pj);
   delete pj;
   return rc;
 }
@@ -1243,8 +1433,11 @@ int groth16_prove_resident(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, 
                            const uint64_t r[4], const uint64_t s[4], uint64_t a_out[8], uint64_t b_out[16],
                            uint64_t c_out[8]) {
   zkmi_proof_job* pj = nullptr;
-  ZK_TRY(groth16_prove_submit(ctx, pk, dr, dz, r, s, &pj));
-  return groth16_prove_wait(pj, a_out, b_out, c_out);
+  ZK_TRY(groth16_prove_submit(ctx, pk, dr, dz, r, s, ctx->prove_check != 0, &pj));
+  std::vector<zkmi_r1cs_status> st;
+  const int rc = groth16_prove_wait(pj, a_out, b_out, c_out, &st);
+  ctx->last_check.swap(st);
+  return rc;
 }
 
 // ------------------------------------------------------------ batched prove
@@ -1271,12 +1464,13 @@ static void proof_job_free(zkmi_proof_job* pj) {
   for (zkmi_proof_job* part : pj->parts) proof_job_free(part);
   for (auto*& j : pj->jobs)
     if (j) msm_job_free(j), j = nullptr;
+  chk_release(pj);
   delete pj;
 }
 
 // one group: batch i's assignment at dz + i * zstr words
 static int prove_group_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& dr, const uint32_t* dz, size_t zstr,
-                              size_t gnb, uint32_t logn, zkmi_proof_job* pj) {
+                              size_t gnb, uint32_t logn, zkmi_proof_job* pj, bool check) {
   const size_t l = dr.l, w = dr.w, nv = l + w, n = pk->n;
   const int nl = std::max(1, ctx->msm_lanes);
   const size_t zsb = zstr * 4;  // bytes
@@ -1291,8 +1485,13 @@ static int prove_group_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& d
         dz, pk->d_bidx, pk->nb_c, zb, zstr);
     ZK_HIP(hipGetLastError());
   }
+  ChkReq chk_req, *chk = nullptr;  // (as groth16_prove_submit: the group's gnb statuses, an event of its own)
+  if (check) {
+    ZK_TRY(chk_acquire(ctx, pj, gnb, &chk_req));
+    chk = &chk_req;
+  }
   ZK_HIP(hipEventRecord(ctx->prove_fork, ctx->stream));
-  ZK_TRY(witness_map_many(ctx, dr, dz, zstr, (unsigned)gnb, logn, dv));
+  ZK_TRY(witness_map_many(ctx, dr, dz, zstr, (unsigned)gnb, logn, dv, chk));
   ctx->msm_fork = ctx->prove_fork;
   int rc = 0;
   ctx->lane_next = 1 % nl;
@@ -1339,6 +1538,7 @@ int groth16_prove_many_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& d
   mj->zstr = z_stride / 4;
   mj->rs.assign(r, r + 4 * nb);
   mj->ss.assign(s, s + 4 * nb);
+  mj->check = ctx->prove_check != 0;
   int rc = 0;
   if (pk->n <= SMALL_PROOF_MAX) {
     const size_t G = (size_t)prove_group_size(ctx, pk->n);
@@ -1352,7 +1552,7 @@ int groth16_prove_many_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& d
       pj->ss.assign(s + 4 * b0, s + 4 * (b0 + gnb));
       pj->asms.resize(gnb);
       mj->parts.push_back(pj);
-      rc = prove_group_submit(ctx, pk, dr, dz + b0 * mj->zstr, mj->zstr, gnb, logn, pj);
+      rc = prove_group_submit(ctx, pk, dr, dz + b0 * mj->zstr, mj->zstr, gnb, logn, pj, mj->check);
       // the key-only part of each assembly while the GPU works
       for (size_t i = 0; i < gnb && !rc; i++)
         groth16_asm_fixed_tab(pk->asm_d1.data(), pk->asm_d2.data(), &pj->rs[4 * i], &pj->ss[4 * i], &pj->asms[i]);
@@ -1361,7 +1561,8 @@ int groth16_prove_many_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& d
   } else {
     for (; mj->next < std::min<size_t>(nb, 2) && !rc; mj->next++) {
       zkmi_proof_job* pj = nullptr;
-      rc = groth16_prove_submit(ctx, pk, dr, dz + mj->next * mj->zstr, r + 4 * mj->next, s + 4 * mj->next, &pj);
+      rc = groth16_prove_submit(ctx, pk, dr, dz + mj->next * mj->zstr, r + 4 * mj->next, s + 4 * mj->next,
+                                mj->check, &pj);
       if (!rc) mj->parts.push_back(pj);
     }
   }
@@ -1374,7 +1575,8 @@ int groth16_prove_many_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const DevR1CS& d
 }
 
 // a group's MSM results -> its gnb proofs (groth16_prove_wait's order of stages)
-static int prove_group_wait(zkmi_proof_job* pj, uint64_t* a_out, uint64_t* b_out, uint64_t* c_out) {
+static int prove_group_wait(zkmi_proof_job* pj, uint64_t* a_out, uint64_t* b_out, uint64_t* c_out,
+                            std::vector<zkmi_r1cs_status>* chk_out) {
   const zkmi_pk* pk = pj->pk;
   zkmi_msm_job** jobs = pj->jobs;
   const size_t g = pj->gnb;
@@ -1392,11 +1594,13 @@ static int prove_group_wait(zkmi_proof_job* pj, uint64_t* a_out, uint64_t* b_out
   if (!rc) rc = msm_batch_wait(jobs[0], h_acc.data(), g), jobs[0] = nullptr;
   for (size_t i = 0; i < g && !rc; i++)
     groth16_asm_c(&l_acc[8 * i], &h_acc[8 * i], &pj->asms[i], a_out + 8 * i, c_out + 8 * i);
+  if (!rc && pj->check) rc = chk_collect(pj, g, chk_out);
   proof_job_free(pj);
   return rc;
 }
 
 int groth16_prove_many_wait(zkmi_proof_job* mj, size_t nb, uint64_t* a_out, uint64_t* b_out, uint64_t* c_out) {
+  std::vector<zkmi_r1cs_status> st;  // the parts' statuses, in proof order
   int rc = 0;
   size_t at = 0;
   // (parts grows while it is walked above the small schedule: index, not iterator)
@@ -1409,20 +1613,23 @@ int groth16_prove_many_wait(zkmi_proof_job* mj, size_t nb, uint64_t* a_out, uint
     }
     if (pj->gnb) {
       const size_t g = pj->gnb;
-      rc = prove_group_wait(pj, a_out + 8 * at, b_out + 16 * at, c_out + 8 * at);
+      rc = prove_group_wait(pj, a_out + 8 * at, b_out + 16 * at, c_out + 8 * at, &st);
       at += g;
     } else {
-      rc = groth16_prove_wait(pj, a_out + 8 * at, b_out + 16 * at, c_out + 8 * at);
+      rc = groth16_prove_wait(pj, a_out + 8 * at, b_out + 16 * at, c_out + 8 * at, &st);
       at++;
       if (!rc && mj->next < mj->nb) {  // keep two in flight
         zkmi_proof_job* nx = nullptr;
+        // (the check as sampled at submit, whatever the context holds now)
         rc = groth16_prove_submit(mj->ctx, mj->pk, *mj->dr, mj->dz + mj->next * mj->zstr, &mj->rs[4 * mj->next],
-                                  &mj->ss[4 * mj->next], &nx);
+                                  &mj->ss[4 * mj->next], mj->check, &nx);
         if (!rc) mj->parts.push_back(nx), mj->next++;
       }
     }
   }
   mj->parts.clear();
+  if (rc) st.clear();
+  mj->ctx->last_check.swap(st);
   proof_job_free(mj);
   return rc;
 }
@@ -1890,6 +2097,37 @@ int zkmi_r1cs_create(zkmi_ctx* ctx, const zkmi_r1cs* cs, zkmi_r1cs_dev** out) {
 void zkmi_r1cs_destroy(zkmi_r1cs_dev* d) {
   delete d;
 }
+int zkmi_r1cs_check(zkmi_ctx* ctx, const zkmi_r1cs_dev* cs, const void* d_z, size_t nb, size_t z_stride,
+                    zkmi_r1cs_status* out) {
+  ZK_DEVICE_GUARD(ctx);
+  if (!ctx || !cs || (nb && (!d_z || !out))) {
+    set_error("zkmi_r1cs_check: null argument");
+    return ZKMI_EINVAL;
+  }
+  return r1cs_check(ctx, *cs, (const uint32_t*)d_z, nb, z_stride, out);
+}
+int zkmi_ctx_set_prove_check(zkmi_ctx* ctx, int on) {
+  if (!ctx) {
+    set_error("zkmi_ctx_set_prove_check: null context");
+    return ZKMI_EINVAL;
+  }
+  ctx->prove_check = on != 0;
+  return 0;
+}
+int zkmi_ctx_get_prove_check(const zkmi_ctx* ctx) { return ctx ? ctx->prove_check : -1; }
+int zkmi_groth16_last_check(zkmi_ctx* ctx, zkmi_r1cs_status* out, size_t cap, size_t* count) {
+  if (!ctx || !count) {
+    set_error("zkmi_groth16_last_check: null argument");
+    return ZKMI_EINVAL;
+  }
+  *count = ctx->last_check.size();
+  if (cap < *count || (*count && !out)) {
+    set_error("zkmi_groth16_last_check: %zu statuses, room for %zu", *count, cap);
+    return ZKMI_EINVAL;
+  }
+  if (*count) memcpy(out, ctx->last_check.data(), *count * sizeof(zkmi_r1cs_status));
+  return 0;
+}
 int zkmi_groth16_prove_resident(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_dev* cs, const void* d_z,
                                 const uint64_t r[4], const uint64_t s[4], uint64_t a_out[8], uint64_t b_out[16],
                                 uint64_t c_out[8]) {
@@ -1909,7 +2147,7 @@ int zkmi_groth16_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_
     set_error("zkmi_groth16_prove_submit: null argument");
     return ZKMI_EINVAL;
   }
-  return groth16_prove_submit(ctx, pk, *cs, (const uint32_t*)d_z, r, s, job);
+  return groth16_prove_submit(ctx, pk, *cs, (const uint32_t*)d_z, r, s, ctx->prove_check != 0, job);
 }
 int zkmi_groth16_prove_wait(zkmi_proof_job* job, uint64_t a_out[8], uint64_t b_out[16], uint64_t c_out[8]) {
   if (!job || !a_out || !b_out || !c_out) {
@@ -1922,7 +2160,9 @@ int zkmi_groth16_prove_wait(zkmi_proof_job* job, uint64_t a_out[8], uint64_t b_o
   }
   zkmi_ctx* ctx = job->pk->ctx;
   ZK_DEVICE_GUARD(ctx);
-  int rc = groth16_prove_wait(job, a_out, b_out, c_out);
+  std::vector<zkmi_r1cs_status> st;
+  int rc = groth16_prove_wait(job, a_out, b_out, c_out, &st);
+  ctx->last_check.swap(st);
   if (rc == 0) rc = timer_flush(ctx, false);
   return rc;
 }

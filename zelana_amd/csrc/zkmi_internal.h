@@ -95,6 +95,10 @@ struct zkmi_ctx {
   hipEvent_t acc_gate = nullptr;
   const zkmi_bases* acc_gate_set = nullptr;
   hipEvent_t wm_done = nullptr;  // owned: end of a large proof's witness map
+  // R1CS check of the prove path (zkmi_ctx_set_prove_check): sampled by a
+  // proof job at submit; last_check holds the statuses of the job waited last
+  int prove_check = 0;
+  std::vector<zkmi_r1cs_status> last_check;
   // Stream budget: communicators alive on this context, and the
   // streams the library holds for it (context, lanes, communicators', witness
   // programs').  While a communicator exists the lanes are capped at

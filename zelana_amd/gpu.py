@@ -7,10 +7,11 @@ from __future__ import annotations
 
 import ctypes
 import weakref
+from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import R1CSStruct, ZkmiError, check, lib, u64p, u8p, vp
+from ._lib import ROW_NONE, R1CSStatusStruct, R1CSStruct, ZkmiError, check, lib, u64p, u8p, vp
 
 
 def _p64(a: np.ndarray):
@@ -163,6 +164,14 @@ class Context:
 
     def batch_group(self) -> int:
         return lib().zkmi_ctx_get_batch_group(self.h)
+
+    def set_prove_check(self, on: bool):
+        """Proof jobs submitted while on also check their witness against the
+        R1CS (groth16_last_check after the wait); off by default."""
+        check(lib().zkmi_ctx_set_prove_check(self.h, int(bool(on))), "zkmi_ctx_set_prove_check")
+
+    def prove_check(self) -> bool:
+        return lib().zkmi_ctx_get_prove_check(self.h) == 1
 
     def set_lanes(self, lanes: int):
         """MSM lanes (capped at 2 while a communicator exists: stream budget)."""
@@ -584,6 +593,50 @@ class R1CSDevice:
             self.close()
         except Exception:
             pass
+
+
+@dataclass
+class R1CSStatus:
+    """zkmi_r1cs_status: first_row is the lowest row with <a,z><b,z> != <c,z>
+    (None if every row holds), n_bad the number of such rows, a / b / c the
+    three canonical values at first_row (0 if none)."""
+    first_row: int | None
+    n_bad: int
+    a: int
+    b: int
+    c: int
+
+    @property
+    def ok(self) -> bool:
+        return self.first_row is None
+
+
+def _statuses(arr, count: int) -> list[R1CSStatus]:
+    def val(w):
+        return sum(int(w[k]) << (64 * k) for k in range(4))
+
+    return [R1CSStatus(None if arr[i].first_row == ROW_NONE else int(arr[i].first_row), int(arr[i].n_bad),
+                       val(arr[i].a), val(arr[i].b), val(arr[i].c)) for i in range(count)]
+
+
+def r1cs_check(ctx: Context, r1cs: R1CSDevice, dz: DeviceBuffer, nb: int = 1, stride: int | None = None):
+    """Row satisfaction of nb resident assignments (assignment i at dz + i *
+    stride bytes, default packed) against a resident R1CS: [R1CSStatus]."""
+    if stride is None:
+        stride = r1cs.num_variables * 32
+    out = (R1CSStatusStruct * max(1, nb))()
+    check(lib().zkmi_r1cs_check(ctx.h, r1cs.h, dz.ptr, nb, stride, out), "zkmi_r1cs_check")
+    return _statuses(out, nb)
+
+
+def groth16_last_check(ctx: Context) -> list[R1CSStatus]:
+    """Statuses of the proofs of the proof job most recently waited on ctx, in
+    proof order; [] if it was submitted with the check off."""
+    cnt = ctypes.c_size_t()
+    lib().zkmi_groth16_last_check(ctx.h, None, 0, ctypes.byref(cnt))  # (EINVAL when there are any: count only)
+    out = (R1CSStatusStruct * max(1, cnt.value))()
+    check(lib().zkmi_groth16_last_check(ctx.h, out, cnt.value, ctypes.byref(cnt)), "zkmi_groth16_last_check")
+    return _statuses(out, cnt.value)
 
 
 def synthetic_pk(ctx: Context, seed: int, log_n: int, num_instance: int, num_witness: int) -> "ProvingKey":

@@ -113,13 +113,23 @@ class BatchProof:
     a: np.ndarray | None = field(default=None, repr=False)
     b: np.ndarray | None = field(default=None, repr=False)
     c: np.ndarray | None = field(default=None, repr=False)
+    # extra: the R1CS check of the witness this proof was made from (a prover
+    # with check=True).  None = not checked; first_unsatisfied = the lowest
+    # constraint that does not hold.  The proof is made either way, as the
+    # reference (arkworks in release mode) makes it.
+    constraints_ok: bool | None = None
+    first_unsatisfied: int | None = None
 
 
 class Groth16Prover:
     """Drop-in for the reference Groth16Prover on one MI355X (one per process)."""
 
-    def __init__(self, ctx: gpu.Context, pk: gpu.ProvingKey, vk_bytes: bytes, circuit=None):
+    def __init__(self, ctx: gpu.Context, pk: gpu.ProvingKey, vk_bytes: bytes, circuit=None, check: bool = False):
         self.ctx = ctx
+        # check the witness of every proof against the R1CS on the GPU (the scan
+        # rides on the witness map's mat-vecs): BatchProof.constraints_ok /
+        # first_unsatisfied; nothing is raised here
+        self.check = check
         self.pk = pk
         self.verifying_key = vk_bytes
         self.vk_hash = blake3(vk_bytes)
@@ -132,7 +142,7 @@ class Groth16Prover:
 
     @classmethod
     def from_bytes(cls, pk_bytes: bytes, vk_bytes: bytes, device: int = 0, circuit=None, compressed=True,
-                   precompute: bool = True):
+                   precompute: bool = True, check: bool = False):
         """ProvingKey/VerifyingKey::deserialize_compressed (validated) -> resident pk.
 
         precompute: build fixed-base tables for the pk queries once here (HBM
@@ -145,10 +155,11 @@ class Groth16Prover:
         vk = gpu.vk_canonical(ctx, vk_bytes)
         if precompute:
             pk.precompute()
-        return cls(ctx, pk, vk, circuit)
+        return cls(ctx, pk, vk, circuit, check)
 
     @classmethod
-    def keygen(cls, device: int = 0, seed: int = 0, circuit_shape=None, precompute: bool = True):
+    def keygen(cls, device: int = 0, seed: int = 0, circuit_shape=None, precompute: bool = True,
+               check: bool = False):
         """prover/src/bin/keygen.rs: Groth16::circuit_specific_setup(L2BlockCircuit::dummy(),
         StdRng::seed_from_u64(seed)) with the key built on the GPU.  Returns
         (prover, pk_bytes, vk_bytes); the bytes are arkworks' serialize_compressed."""
@@ -161,7 +172,7 @@ class Groth16Prover:
         pk_bytes = pk.serialize()
         if precompute:
             pk.precompute()
-        return cls(ctx, pk, vk), pk_bytes, vk
+        return cls(ctx, pk, vk, check=check), pk_bytes, vk
 
     @classmethod
     def from_files(cls, pk_path: str, vk_path: str, **kw):
@@ -170,6 +181,23 @@ class Groth16Prover:
         with open(vk_path, "rb") as f:
             vkb = f.read()
         return cls.from_bytes(pkb, vkb, **kw)
+
+    def _proved(self, call):
+        """(call(), its proofs' statuses or None): one GPU proof call, with the
+        context's prove check on for it when self.check is set."""
+        if not self.check:
+            return call(), None
+        prev = self.ctx.prove_check()
+        self.ctx.set_prove_check(True)
+        try:
+            res = call()
+        finally:
+            self.ctx.set_prove_check(prev)
+        return res, gpu.groth16_last_check(self.ctx)
+
+    @staticmethod
+    def _status_fields(st) -> dict:
+        return {} if st is None else {"constraints_ok": st.first_row is None, "first_unsatisfied": st.first_row}
 
     # ---------------------------------------------------------- BatchProver
     def prove(self, inputs: BatchPublicInputs, witness) -> BatchProof:
@@ -203,9 +231,10 @@ class Groth16Prover:
         r = rng.fr_rand()
         s = rng.fr_rand()
         wp.run(ins, dz)
-        a, b, c = gpu.groth16_prove_resident(self.ctx, self.pk, dev, dz, r, s)
+        (a, b, c), st = self._proved(lambda: gpu.groth16_prove_resident(self.ctx, self.pk, dev, dz, r, s))
         return BatchProof(inputs, self.proof_to_solana_bytes(a, b, c),
-                          int((time.perf_counter() - start) * 1000), a, b, c)
+                          int((time.perf_counter() - start) * 1000), a, b, c,
+                          **self._status_fields(st[0] if st else None))
 
     def prove_many(self, batches) -> list:
         """Proofs of a list of (inputs, witness), in input order, each equal to
@@ -247,10 +276,12 @@ class Groth16Prover:
                 rs.append(rng.fr_rand())
                 ss.append(rng.fr_rand())
             wp.run_many([H.l2_witness_inputs(*batches[i]) for i in idxs], dzm, stride)
-            proofs = gpu.groth16_prove_many(self.ctx, self.pk, dev, dzm, nb, stride, rs, ss)
+            proofs, sts = self._proved(
+                lambda: gpu.groth16_prove_many(self.ctx, self.pk, dev, dzm, nb, stride, rs, ss))
             ms = int((time.perf_counter() - start) * 1000 / nb)
-            for i, (a, b, c) in zip(idxs, proofs):
-                out[i] = BatchProof(batches[i][0], self.proof_to_solana_bytes(a, b, c), ms, a, b, c)
+            for k, (i, (a, b, c)) in enumerate(zip(idxs, proofs)):
+                out[i] = BatchProof(batches[i][0], self.proof_to_solana_bytes(a, b, c), ms, a, b, c,
+                                    **self._status_fields(sts[k] if sts else None))
         return out
 
     def prove_r1cs(self, cs, z, inputs: BatchPublicInputs) -> BatchProof:
@@ -258,9 +289,10 @@ class Groth16Prover:
         rng = StdRng.seed_from_u64(inputs.batch_id)
         r = rng.fr_rand()
         s = rng.fr_rand()
-        a, b, c = gpu.groth16_prove(self.ctx, self.pk, cs, _as_z(z), r, s)
+        (a, b, c), st = self._proved(lambda: gpu.groth16_prove(self.ctx, self.pk, cs, _as_z(z), r, s))
         return BatchProof(inputs, self.proof_to_solana_bytes(a, b, c),
-                          int((time.perf_counter() - start) * 1000), a, b, c)
+                          int((time.perf_counter() - start) * 1000), a, b, c,
+                          **self._status_fields(st[0] if st else None))
 
     def verify(self, proof: BatchProof) -> bool:
         # reference semantics (prover.rs:427-442): length check only
