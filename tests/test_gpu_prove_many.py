@@ -121,6 +121,9 @@ def _run_batch(ctx, bases, vs, n, pad, offset=0, pts=None):
 MSM_CASES = [
     ("radix_c8", "plain", 700, 3, 8, 64, 0, 0),
     ("plain_auto_c13", "big", 20000, 2, 0, 64, 64, 0),
+    # 11 bin-sort chunks per vector (the last partial) x 3 vectors = 33 > 32 super-chunks, so they pair up
+    # and super-chunk 5 holds the last chunk of vector 0 and the first of vector 1
+    ("bin_sort_superchunk_across_vectors", "big", 11000, 3, 13, 64, 64, 0),
     ("table_counting_sort", "full", 3000, 4, 0, 64, 0, 0),
     ("table_bin_sort", "full", 3000, 5, 0, 64, 64, 0),
     ("table_small_split_K16", "full", 700, 16, 0, 64, 0, 0),

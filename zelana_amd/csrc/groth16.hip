@@ -294,22 +294,20 @@ __device__ __forceinline__ Fe mv_term(uint64_t k, const uint64_t* __restrict__ c
     return mul<FrP>(ld_fe(val + k * 8), ld_fe(zm + col[k] * 8));
   }
 }
-// BAT (batched witness map): blockIdx.y is the assignment: z at zc + y * zstr
-// words (its Montgomery copy at zm + y * zmstr), the output vector at out + y
-// * n elements; the matrices are shared.
-template <bool DICT, class RP, bool BAT = false>
+// blockIdx.y is the assignment (one row for a single witness map): z at zc + y
+// * zstr words (its Montgomery copy at zm + y * zmstr), the output vector at
+// out + y * n elements; the matrices are shared.
+template <bool DICT, class RP>
 __global__ void __launch_bounds__(256) k_matvec(const RP* __restrict__ rowptr, const uint64_t* __restrict__ col,
                                                 const uint32_t* __restrict__ val, const uint2* __restrict__ cv,
                                                 const uint32_t* __restrict__ coef, const uint32_t* __restrict__ zm,
                                                 const uint32_t* __restrict__ zc, size_t m, size_t l, size_t n,
                                                 int is_a, const uint32_t* __restrict__ lrow, uint32_t nlong, int g,
-                                                uint32_t nsb, uint32_t* __restrict__ out, size_t zstr = 0,
-                                                size_t zmstr = 0) {
-  if (BAT) {
-    zc += (size_t)blockIdx.y * zstr;
-    if (!DICT) zm += (size_t)blockIdx.y * zmstr;
-    out += (size_t)blockIdx.y * n * 8;
-  }
+                                                uint32_t nsb, uint32_t* __restrict__ out, size_t zstr,
+                                                size_t zmstr) {
+  zc += (size_t)blockIdx.y * zstr;
+  if (!DICT) zm += (size_t)blockIdx.y * zmstr;
+  out += (size_t)blockIdx.y * n * 8;
   if (blockIdx.x < nsb) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -724,6 +722,35 @@ struct ChkReq {
   hipEvent_t done;
 };
 
+// The mat-vecs of nb assignments (z_i at d_z + i * zstr words) into a, b, c (nb
+// vectors of n elements each; zm: nb x nv x 32 B for the legacy form, which
+// multiplies canonical coefficients by a Montgomery copy of z, else unused).  is_a:
+// A's vectors also take the input copies in rows m .. m + l (the witness map);
+// n = m with is_a = 0 writes the rows alone (the stand-alone check).
+static int matvec_many(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, size_t zstr, unsigned nb, size_t n,
+                       int is_a, uint32_t* zm, uint32_t* a, uint32_t* b, uint32_t* c) {
+  hipStream_t st = ctx->stream;
+  const size_t m = dr.m, l = dr.l, nv = l + dr.w;
+  const bool legacy = !dr.dict[0] || !dr.dict[1] || !dr.dict[2];
+  const unsigned gn = (unsigned)((n + 255) / 256);
+  ScopedKernelTimer tm(ctx, "g16_matvec");
+  if (legacy) k_to_mont_fr<<<dim3((unsigned)((nv + 255) / 256), nb), 256, 0, st>>>(d_z, nv, zm, zstr);
+  uint32_t* outs[3] = {a, b, c};
+  for (int t = 0; t < 3; t++) {
+    const unsigned gl = (unsigned)(((size_t)dr.nlong[t] * dr.glong[t] + 255) / 256);
+    if (dr.dict[t])
+      k_matvec<true, uint32_t><<<dim3(gn + gl, nb), 256, 0, st>>>(
+          dr.rp32[t], nullptr, nullptr, dr.cv[t], dr.coef[t], zm, d_z, m, l, n, is_a && t == 0, dr.lrow[t],
+          dr.nlong[t], dr.glong[t], gn, outs[t], zstr, nv * 8);
+    else
+      k_matvec<false, uint64_t><<<dim3(gn + gl, nb), 256, 0, st>>>(
+          dr.rp[t], dr.col[t], dr.val[t], nullptr, nullptr, zm, d_z, m, l, n, is_a && t == 0, dr.lrow[t],
+          dr.nlong[t], dr.glong[t], gn, outs[t], zstr, nv * 8);
+  }
+  ZK_HIP(hipGetLastError());
+  return 0;
+}
+
 // h (bit-reversed layout, canonical, n elements) into d_h from device z
 static int witness_map_dev(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, uint32_t logn, uint32_t* d_h,
                            const ChkReq* chk = nullptr) {
@@ -739,26 +766,7 @@ static int witness_map_dev(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z
   ZK_TRY(ctx->ws.get("wm_c", n * 32, (void**)&c));
   uint32_t* a = d_h;
   unsigned gn = (unsigned)((n + 255) / 256);
-  {
-    ScopedKernelTimer tm(ctx, "g16_matvec");
-    // (the legacy form multiplies canonical coefficients by a Montgomery copy
-    // of z; the compact form needs none)
-    if (!dr.dict[0] || !dr.dict[1] || !dr.dict[2])
-      k_to_mont_fr<<<(unsigned)((nv + 255) / 256), 256, 0, st>>>(d_z, nv, zm);
-    uint32_t* outs[3] = {a, b, c};
-    for (int t = 0; t < 3; t++) {
-      const unsigned gl = (unsigned)(((size_t)dr.nlong[t] * dr.glong[t] + 255) / 256);
-      if (dr.dict[t])
-        k_matvec<true, uint32_t><<<gn + gl, 256, 0, st>>>(dr.rp32[t], nullptr, nullptr, dr.cv[t], dr.coef[t], zm,
-                                                          d_z, m, l, n, t == 0, dr.lrow[t], dr.nlong[t],
-                                                          dr.glong[t], gn, outs[t]);
-      else
-        k_matvec<false, uint64_t><<<gn + gl, 256, 0, st>>>(dr.rp[t], dr.col[t], dr.val[t], nullptr, nullptr, zm,
-                                                           d_z, m, l, n, t == 0, dr.lrow[t], dr.nlong[t],
-                                                           dr.glong[t], gn, outs[t]);
-    }
-    ZK_HIP(hipGetLastError());
-  }
+  ZK_TRY(matvec_many(ctx, dr, d_z, 0, 1, n, 1, zm, a, b, c));
   if (chk) ZK_TRY(r1cs_scan_queue(ctx, a, b, c, m, 0, 1, chk->host, chk->done));
   // evaluations -> coefficients (DIF, bit-reversed) -> * n^-1 g^i -> coset
   // evaluations (DIT, natural)
@@ -783,34 +791,6 @@ static int witness_map_dev(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z
 // b's, then the c's -- so each NTT direction is one batched launch sequence
 // over all 3 nb of them; h_i (bit-reversed layout, as witness_map_dev) ends up
 // in a_i = d_v + i * n elements.  ws: nb (3 n [+ nv]) x 32 B.
-// the batched mat-vecs of nb assignments into a, b, c (nb vectors of n
-// elements each; zm: nb x nv x 32 B for the legacy form, else unused).  is_a:
-// A's vectors also take the input copies in rows m .. m + l (the witness map);
-// n = m with is_a = 0 writes the rows alone (the stand-alone check).
-static int matvec_many(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, size_t zstr, unsigned nb, size_t n,
-                       int is_a, uint32_t* zm, uint32_t* a, uint32_t* b, uint32_t* c) {
-  hipStream_t st = ctx->stream;
-  const size_t m = dr.m, l = dr.l, nv = l + dr.w;
-  const bool legacy = !dr.dict[0] || !dr.dict[1] || !dr.dict[2];
-  const unsigned gn = (unsigned)((n + 255) / 256);
-  ScopedKernelTimer tm(ctx, "g16_matvec");
-  if (legacy) k_to_mont_fr<<<dim3((unsigned)((nv + 255) / 256), nb), 256, 0, st>>>(d_z, nv, zm, zstr);
-  uint32_t* outs[3] = {a, b, c};
-  for (int t = 0; t < 3; t++) {
-    const unsigned gl = (unsigned)(((size_t)dr.nlong[t] * dr.glong[t] + 255) / 256);
-    if (dr.dict[t])
-      k_matvec<true, uint32_t, true><<<dim3(gn + gl, nb), 256, 0, st>>>(
-          dr.rp32[t], nullptr, nullptr, dr.cv[t], dr.coef[t], zm, d_z, m, l, n, is_a && t == 0, dr.lrow[t],
-          dr.nlong[t], dr.glong[t], gn, outs[t], zstr, nv * 8);
-    else
-      k_matvec<false, uint64_t, true><<<dim3(gn + gl, nb), 256, 0, st>>>(
-          dr.rp[t], dr.col[t], dr.val[t], nullptr, nullptr, zm, d_z, m, l, n, is_a && t == 0, dr.lrow[t],
-          dr.nlong[t], dr.glong[t], gn, outs[t], zstr, nv * 8);
-  }
-  ZK_HIP(hipGetLastError());
-  return 0;
-}
-
 static int witness_map_many(zkmi_ctx* ctx, const DevR1CS& dr, const uint32_t* d_z, size_t zstr, unsigned nb,
                             uint32_t logn, uint32_t* d_v, const ChkReq* chk = nullptr) {
   hipStream_t st = ctx->stream;

@@ -32,6 +32,7 @@
 #include <algorithm>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 #include <chrono>
 
@@ -193,20 +194,18 @@ __device__ __forceinline__ void scalar_digits(const uint32_t* __restrict__ scala
 // (p = 1, Wp = W without a table).  Digits depend on the scalars only (bases
 // at infinity are skipped in the accumulation), so MSMs with the same
 // scalars over different base sets share one sort (msm_submit_shared).
-// BAT (batched MSMs, msm_batch_submit): blockIdx.y is the batch; it reads the
-// scalar vector at scalars + batch * sstride words and writes the batch's
-// Wp * p * n digits after those of the batches before it, so the sort sees
-// nb * Wp windows (the batch index is an outer window).
-template <int C, bool BAL, bool BAT = false>
+// blockIdx.y is the scalar vector (batched MSMs, msm_batch_submit; a single
+// MSM is a grid of one row): it reads the vector at scalars + y * sstride words
+// and writes its Wp * p * n digits after those of the vectors before it, so the
+// sort sees nb * Wp windows (the vector index is an outer window).
+template <int C, bool BAL>
 __global__ void __launch_bounds__(256) k_msm_digits(const uint32_t* __restrict__ scalars, size_t n, int p, int Wp,
-                                                    int32_t* __restrict__ digits, size_t sstride = 0) {
+                                                    int32_t* __restrict__ digits, size_t sstride) {
   ZK_TAIL_WAVE();
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  if (BAT) {
-    scalars += (size_t)blockIdx.y * sstride;
-    digits += (size_t)blockIdx.y * (size_t)Wp * p * n;
-  }
+  scalars += (size_t)blockIdx.y * sstride;
+  digits += (size_t)blockIdx.y * (size_t)Wp * p * n;
   constexpr int W = msm_windows(C);
   int32_t d[W];
   scalar_digits<C, BAL>(scalars, i, d);
@@ -418,8 +417,11 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_p1_scatter(const int32_t* __r
 template <int C, bool BAL>
 // wsel (window-sharded MSMs, plain plans): windows [w0, w0 + wn) only, keyed
 // from window w0 on (wsel = w0 | wn << 16; 0 = every window)
+// kbase: the key of the scalar vector's window 0 (vector index * Wp * B: the
+// vector is an outer window; 0 for a single MSM)
 __device__ __forceinline__ void rs_scalar_keys(const uint32_t* __restrict__ scalars, size_t i, size_t n, int Wp,
-                                               uint32_t B, uint32_t* key, uint32_t* val, bool* ok, uint32_t wsel) {
+                                               uint32_t B, uint32_t* key, uint32_t* val, bool* ok, uint32_t wsel,
+                                               uint32_t kbase) {
   constexpr int W = msm_windows(C);
   int32_t d[W];
   scalar_digits<C, BAL>(scalars, i, d);
@@ -430,7 +432,7 @@ __device__ __forceinline__ void rs_scalar_keys(const uint32_t* __restrict__ scal
     const int32_t v = d[w];
     const uint32_t wr = (uint32_t)w - w0;
     ok[w] = v != 0 && (wn == 0 || wr < wn);
-    key[w] = (wn ? wr : wq) * B + (uint32_t)(v < 0 ? -v : v) - 1;
+    key[w] = kbase + (wn ? wr : wq) * B + (uint32_t)(v < 0 ? -v : v) - 1;
     val[w] = (uint32_t)(j * n + i) | (v < 0 ? 0x80000000u : 0u);
     if (++wq == (uint32_t)Wp) {
       wq = 0;
@@ -448,24 +450,24 @@ __device__ __forceinline__ void rs_scalar_keys(const uint32_t* __restrict__ scal
 // Order inside a bucket is then arbitrary, as everywhere (group addition is
 // exact).  Contention stays low: ~30 entries per bucket.
 constexpr size_t SMALL_SORT_MAX = (size_t)1 << 18;
-// BAT (batched MSMs): blockIdx.y is the batch: its scalars start sstride words
-// further per batch and its keys Wp * B further (the batch is an outer window);
-// values are unchanged (every batch gathers the same table rows).
-template <int C, bool BAL, bool BAT = false>
+// blockIdx.y is the scalar vector (one row for a single MSM): its scalars
+// start sstride words further per vector and its keys Wp * B further (the
+// vector is an outer window); values are unchanged (every vector gathers the
+// same table rows).
+template <int C, bool BAL>
 __global__ void __launch_bounds__(256) k_ss_count(const uint32_t* __restrict__ scalars, size_t n, int Wp, uint32_t B,
-                                                  uint32_t wsel, uint32_t* __restrict__ cnt, size_t sstride = 0) {
+                                                  uint32_t wsel, uint32_t* __restrict__ cnt, size_t sstride) {
   ZK_TAIL_WAVE();
   constexpr int W = msm_windows(C);
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t key[W], val[W];
   bool ok[W];
-  if (BAT) scalars += (size_t)blockIdx.y * sstride;
-  rs_scalar_keys<C, BAL>(scalars, i, n, Wp, B, key, val, ok, wsel);
-  const uint32_t koff = BAT ? blockIdx.y * (uint32_t)Wp * B : 0u;
+  scalars += (size_t)blockIdx.y * sstride;
+  rs_scalar_keys<C, BAL>(scalars, i, n, Wp, B, key, val, ok, wsel, blockIdx.y * (uint32_t)Wp * B);
 #pragma unroll
   for (int w = 0; w < W; w++)
-    if (ok[w]) atomicAdd(&cnt[key[w] + koff], 1u);
+    if (ok[w]) atomicAdd(&cnt[key[w]], 1u);
 }
 // one 1024-thread workgroup: bstart[k] = sum of cnt[< k], bstart[K] = total,
 // cursor = a copy of bstart[0..K)
@@ -500,22 +502,21 @@ __global__ void __launch_bounds__(1024) k_ss_scan(uint32_t* __restrict__ cnt, ui
   }
   if (threadIdx.x == 0) bstart[K] = total;
 }
-template <int C, bool BAL, bool BAT = false>
+template <int C, bool BAL>
 __global__ void __launch_bounds__(256) k_ss_scatter(const uint32_t* __restrict__ scalars, size_t n, int Wp,
                                                     uint32_t B, uint32_t wsel, uint32_t* __restrict__ cursor,
-                                                    uint32_t* __restrict__ sval, size_t sstride = 0) {
+                                                    uint32_t* __restrict__ sval, size_t sstride) {
   ZK_TAIL_WAVE();
   constexpr int W = msm_windows(C);
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t key[W], val[W];
   bool ok[W];
-  if (BAT) scalars += (size_t)blockIdx.y * sstride;
-  rs_scalar_keys<C, BAL>(scalars, i, n, Wp, B, key, val, ok, wsel);
-  const uint32_t koff = BAT ? blockIdx.y * (uint32_t)Wp * B : 0u;
+  scalars += (size_t)blockIdx.y * sstride;
+  rs_scalar_keys<C, BAL>(scalars, i, n, Wp, B, key, val, ok, wsel, blockIdx.y * (uint32_t)Wp * B);
 #pragma unroll
   for (int w = 0; w < W; w++)
-    if (ok[w]) sval[atomicAdd(&cursor[key[w] + koff], 1u)] = val[w];
+    if (ok[w]) sval[atomicAdd(&cursor[key[w]], 1u)] = val[w];
 }
 
 // one workgroup: bin starts and tile starts (tiles of <= C2 entries per bin)
@@ -721,37 +722,38 @@ __device__ __forceinline__ uint32_t block_prefix(uint32_t nb, Get get, uint32_t*
   return total;
 }
 
-// BAT (batched MSMs): the chunks of batch q are workgroups [q * nfb, (q + 1)
-// * nfb); a chunk reads its batch's scalar vector (sstride words apart) and
-// offsets its keys by batch * Wp * B.  Chunk offsets, super-chunks and bins
-// work on the flat chunk index as before.
-template <int C, bool BAL, bool BAT = false>
+// Grid (chunks per scalar vector, vectors): workgroup (x, y) is chunk x of
+// vector y (one row for a single MSM); it reads that vector (sstride words per
+// vector) and bases its keys at y * Wp * B.  Chunk offsets, super-chunks and
+// the clearing of next_ctr go by the flat chunk index y * gridDim.x + x.
+template <int C, bool BAL>
 __global__ void __launch_bounds__(256) k_bs_count(const uint32_t* __restrict__ scalars, size_t n, int Wp, uint32_t B,
                                                   uint32_t wsel, uint32_t NH, uint32_t lob, uint32_t CS, uint32_t scs,
                                                   uint32_t* __restrict__ bintot, uint32_t* __restrict__ sctot,
                                                   uint32_t* __restrict__ choff, uint32_t* __restrict__ next_ctr,
-                                                  uint32_t ctr_words, uint32_t nfb = 0, size_t sstride = 0) {
+                                                  uint32_t ctr_words, size_t sstride) {
   ZK_TAIL_WAVE();
   extern __shared__ uint32_t hist[];
   constexpr int W = msm_windows(C);
+  const uint32_t chunk = blockIdx.y * gridDim.x + blockIdx.x;
   // the lane's other counter block, for its next sort
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < ctr_words; i += (size_t)gridDim.x * 256) next_ctr[i] = 0;
+  for (size_t i = (size_t)chunk * 256 + threadIdx.x; i < ctr_words; i += (size_t)gridDim.x * gridDim.y * 256)
+    next_ctr[i] = 0;
   for (uint32_t x = threadIdx.x; x < NH; x += 256) hist[x] = 0;
   __syncthreads();
-  const uint32_t bq = BAT ? blockIdx.x / nfb : 0u;
-  const size_t base = (size_t)(BAT ? blockIdx.x - bq * nfb : blockIdx.x) * CS;
-  const uint32_t koff = BAT ? bq * (uint32_t)Wp * B : 0u;
-  if (BAT) scalars += (size_t)bq * sstride;
+  const size_t base = (size_t)blockIdx.x * CS;
+  const uint32_t kbase = blockIdx.y * (uint32_t)Wp * B;
+  scalars += (size_t)blockIdx.y * sstride;
   for (uint32_t k = threadIdx.x; k < CS && base + k < n; k += 256) {
     uint32_t key[W], val[W];
     bool ok[W];
-    rs_scalar_keys<C, BAL>(scalars, base + k, n, Wp, B, key, val, ok, wsel);
+    rs_scalar_keys<C, BAL>(scalars, base + k, n, Wp, B, key, val, ok, wsel, kbase);
 #pragma unroll
     for (int w = 0; w < W; w++)
-      if (ok[w]) atomicAdd(&hist[(key[w] + koff) >> lob], 1u);
+      if (ok[w]) atomicAdd(&hist[key[w] >> lob], 1u);
   }
   __syncthreads();
-  uint32_t* sc = sctot + (size_t)(blockIdx.x >> scs) * NH;
+  uint32_t* sc = sctot + (size_t)(chunk >> scs) * NH;
   for (uint32_t x = threadIdx.x; x < NH; x += 256) {
     const uint32_t hx = hist[x];
     uint32_t off = 0;
@@ -759,42 +761,38 @@ __global__ void __launch_bounds__(256) k_bs_count(const uint32_t* __restrict__ s
       off = atomicAdd(&sc[x], hx);
       atomicAdd(&bintot[x], hx);
     }
-    choff[(size_t)blockIdx.x * NH + x] = off;
+    choff[(size_t)chunk * NH + x] = off;
   }
 }
 
-// T threads, sub-tiles of T scalars (T * W entries)
-template <int C, int T, bool BAL, bool BAT = false>
+// T threads, sub-tiles of T scalars (T * W entries); the grid of k_bs_count
+template <int C, int T, bool BAL>
 __global__ void __launch_bounds__(T) k_bs_scatter1(const uint32_t* __restrict__ scalars, size_t n, int Wp, uint32_t B,
                                                    uint32_t wsel, uint32_t NH, uint32_t lob, uint32_t CS, uint32_t scs,
                                                    const uint32_t* __restrict__ bintot,
                                                    const uint32_t* __restrict__ sctot,
                                                    const uint32_t* __restrict__ choff, BsKey* __restrict__ okey,
-                                                   uint32_t* __restrict__ oval, uint32_t nfb = 0, size_t sstride = 0) {
+                                                   uint32_t* __restrict__ oval, size_t sstride) {
   ZK_TAIL_WAVE();
   extern __shared__ uint32_t lds[];
   constexpr int W = msm_windows(C);
   uint32_t* gbase = lds + 2 * NH;
   block_prefix<T>(NH, [&](uint32_t k) { return bintot[k]; }, gbase, lds + 3 * NH);
-  const uint32_t s0 = blockIdx.x >> scs;  // this chunk's super-chunk: the earlier ones come first in every bin
+  const uint32_t chunk = blockIdx.y * gridDim.x + blockIdx.x;
+  const uint32_t s0 = chunk >> scs;  // this chunk's super-chunk: the earlier ones come first in every bin
   for (uint32_t x = threadIdx.x; x < NH; x += T) {
-    uint32_t g = gbase[x] + choff[(size_t)blockIdx.x * NH + x];
+    uint32_t g = gbase[x] + choff[(size_t)chunk * NH + x];
     for (uint32_t q = 0; q < s0; q++) g += sctot[(size_t)q * NH + x];
     gbase[x] = g;
   }
-  const uint32_t bq = BAT ? blockIdx.x / nfb : 0u;
-  const size_t base = (size_t)(BAT ? blockIdx.x - bq * nfb : blockIdx.x) * CS;
+  const size_t base = (size_t)blockIdx.x * CS;
   const uint32_t cnt = (uint32_t)std::min<size_t>(CS, n - base);
-  const uint32_t koff = BAT ? bq * (uint32_t)Wp * B : 0u;
-  if (BAT) scalars += (size_t)bq * sstride;
+  const uint32_t kbase = blockIdx.y * (uint32_t)Wp * B;
+  scalars += (size_t)blockIdx.y * sstride;
   auto fill = [&](uint32_t sub, uint32_t* key, uint32_t* val, bool* ok) {
     const uint32_t k = sub * T + threadIdx.x;
     if (k < cnt) {
-      rs_scalar_keys<C, BAL>(scalars, base + k, n, Wp, B, key, val, ok, wsel);
-      if (BAT) {
-#pragma unroll
-        for (int w = 0; w < W; w++) key[w] += koff;
-      }
+      rs_scalar_keys<C, BAL>(scalars, base + k, n, Wp, B, key, val, ok, wsel, kbase);
     } else {
 #pragma unroll
       for (int w = 0; w < W; w++) ok[w] = false;
@@ -2615,66 +2613,41 @@ static int pick_window(size_t n) {
   return 17;
 }
 
-// nb = 0: one MSM (the launches of before); nb >= 1: the batched kernels, one
-// grid row per batch, scalar vectors sstride words apart
-template <int C>
-static void launch_digits(hipStream_t st, const uint32_t* sc, size_t n, int p, int Wp, bool bal, int32_t* dg,
-                          uint32_t nb, size_t sstride) {
-  const unsigned g = (unsigned)((n + 255) / 256);
-  if (nb) {
-    if (bal) k_msm_digits<C, true, true><<<dim3(g, nb), 256, 0, st>>>(sc, n, p, Wp, dg, sstride);
-    else k_msm_digits<C, false, true><<<dim3(g, nb), 256, 0, st>>>(sc, n, p, Wp, dg, sstride);
-    return;
-  }
-  if (bal) k_msm_digits<C, true><<<g, 256, 0, st>>>(sc, n, p, Wp, dg);
-  else k_msm_digits<C, false><<<g, 256, 0, st>>>(sc, n, p, Wp, dg);
+// Calls f(std::integral_constant<int, C>, std::bool_constant<BAL>) for the
+// window c in [CMIN, 22] and the layout bal, so only those windows' kernels are
+// instantiated; `who` prefixes the error of a window outside the range.
+template <int CMIN, class F, int... I>
+static bool window_call(int c, bool bal, F& f, std::integer_sequence<int, I...>) {
+  return ((c == CMIN + I && (bal ? f(std::integral_constant<int, CMIN + I>{}, std::true_type{})
+                                 : f(std::integral_constant<int, CMIN + I>{}, std::false_type{}),
+                             true)) ||
+          ...);
 }
-static int dispatch_digits(int c, hipStream_t st, const uint32_t* sc, size_t n, int p, int Wp, bool bal,
-                           int32_t* dg, uint32_t nb = 0, size_t sstride = 0) {
-  switch (c) {
-#define ZK_C(CC) \
-  case CC: launch_digits<CC>(st, sc, n, p, Wp, bal, dg, nb, sstride); break;
-    ZK_C(4) ZK_C(5) ZK_C(6) ZK_C(7) ZK_C(8) ZK_C(9) ZK_C(10) ZK_C(11) ZK_C(12) ZK_C(13) ZK_C(14) ZK_C(15)
-    ZK_C(16) ZK_C(17) ZK_C(18) ZK_C(19) ZK_C(20) ZK_C(21) ZK_C(22)
-#undef ZK_C
-    default:
-      set_error("unsupported MSM window %d", c);
-      return ZKMI_EINVAL;
-  }
-  return 0;
+template <int CMIN, class F>
+static int dispatch_window(int c, bool bal, const char* who, F f) {
+  if (window_call<CMIN>(c, bal, f, std::make_integer_sequence<int, 22 - CMIN + 1>{})) return 0;
+  set_error("%sunsupported MSM window %d", who, c);
+  return ZKMI_EINVAL;
 }
 
-template <int C, bool BAL>
-static void launch_small_sort(hipStream_t st, const uint32_t* sc, size_t n, int Wp, uint32_t B, uint32_t wsel, uint32_t K,
-                              uint32_t* cnt, uint32_t* cursor, uint32_t* bstart, uint32_t* sval, uint32_t nb,
-                              size_t sstride) {
-  const unsigned g = (unsigned)((n + 255) / 256);
-  if (nb) {  // batched: K covers every batch's windows
-    k_ss_count<C, BAL, true><<<dim3(g, nb), 256, 0, st>>>(sc, n, Wp, B, wsel, cnt, sstride);
-    k_ss_scan<<<1, 1024, 0, st>>>(cnt, K, bstart, cursor);
-    k_ss_scatter<C, BAL, true><<<dim3(g, nb), 256, 0, st>>>(sc, n, Wp, B, wsel, cursor, sval, sstride);
-    return;
-  }
-  k_ss_count<C, BAL><<<g, 256, 0, st>>>(sc, n, Wp, B, wsel, cnt);
-  k_ss_scan<<<1, 1024, 0, st>>>(cnt, K, bstart, cursor);
-  k_ss_scatter<C, BAL><<<g, 256, 0, st>>>(sc, n, Wp, B, wsel, cursor, sval);
+// nb scalar vectors sstride words apart, one grid row each (a single MSM: nb = 1)
+static int dispatch_digits(int c, hipStream_t st, const uint32_t* sc, size_t n, int p, int Wp, bool bal,
+                           int32_t* dg, uint32_t nb, size_t sstride) {
+  const dim3 grid((unsigned)((n + 255) / 256), nb);
+  return dispatch_window<4>(c, bal, "", [&](auto C, auto BAL) {
+    k_msm_digits<C(), BAL()><<<grid, 256, 0, st>>>(sc, n, p, Wp, dg, sstride);
+  });
 }
+
+// K covers every vector's windows
 static int small_sort(int c, bool bal, hipStream_t st, const uint32_t* sc, size_t n, int Wp, uint32_t B, uint32_t wsel, uint32_t K,
-                      uint32_t* cnt, uint32_t* cursor, uint32_t* bstart, uint32_t* sval, uint32_t nb = 0,
-                      size_t sstride = 0) {
-  switch (c) {
-#define ZK_C(CC)                                                                     \
-  case CC:                                                                           \
-    if (bal) launch_small_sort<CC, true>(st, sc, n, Wp, B, wsel, K, cnt, cursor, bstart, sval, nb, sstride); \
-    else launch_small_sort<CC, false>(st, sc, n, Wp, B, wsel, K, cnt, cursor, bstart, sval, nb, sstride);    \
-    break;
-    ZK_C(12) ZK_C(13) ZK_C(14) ZK_C(15) ZK_C(16) ZK_C(17) ZK_C(18) ZK_C(19) ZK_C(20) ZK_C(21) ZK_C(22)
-#undef ZK_C
-    default:
-      set_error("small_sort: unsupported MSM window %d", c);
-      return ZKMI_EINVAL;
-  }
-  return 0;
+                      uint32_t* cnt, uint32_t* cursor, uint32_t* bstart, uint32_t* sval, uint32_t nb, size_t sstride) {
+  const dim3 grid((unsigned)((n + 255) / 256), nb);
+  return dispatch_window<12>(c, bal, "small_sort: ", [&](auto C, auto BAL) {
+    k_ss_count<C(), BAL()><<<grid, 256, 0, st>>>(sc, n, Wp, B, wsel, cnt, sstride);
+    k_ss_scan<<<1, 1024, 0, st>>>(cnt, K, bstart, cursor);
+    k_ss_scatter<C(), BAL()><<<grid, 256, 0, st>>>(sc, n, Wp, B, wsel, cursor, sval, sstride);
+  });
 }
 
 }  // namespace zk
@@ -2745,11 +2718,10 @@ struct MsmPlan {
   // msm_windows(c) the scalars recode into (wsel as rs_scalar_keys)
   int w0 = 0;
   uint32_t wsel = 0;
-  // batched plans (msm_plan_batch): nb scalar vectors, sstride words apart, as
-  // nb x the single plan's windows: W, K and Mmax cover every batch, ne is
-  // still one window's entries
+  // nb scalar vectors, sstride words apart (a single MSM: 1 and 0; batched:
+  // msm_plan_batch), as nb x the single plan's windows: W, K and Mmax cover
+  // every vector, ne is still one window's entries
   int nb = 1;
-  bool batch = false;
   size_t sstride = 0;
   int Wp() const { return wsel ? msm_windows(c) : W / nb; }  // windows per recoded scalar (per table copy)
 };
@@ -2776,7 +2748,6 @@ static MsmPlan msm_plan(const zkmi_ctx* ctx, const zkmi_bases* tb, size_t n) {
 // plan and leaves nb independent sets of bit sums.
 static MsmPlan msm_plan_batch(const zkmi_ctx* ctx, const zkmi_bases* tb, size_t n, int nb, size_t sstride) {
   MsmPlan P = msm_plan(ctx, tb, n);
-  P.batch = true;
   P.nb = nb;
   P.sstride = sstride;
   P.W *= nb;
@@ -2821,7 +2792,7 @@ static uint32_t item_cap(const zkmi_ctx* ctx, const MsmPlan& P) {
 // same stream), so a sort needs no memset launch.
 struct BsGeom {
   uint32_t lob, NLO, NH, CS, nf, scs, C2, T2max;
-  uint32_t nfb;  // chunks per scalar vector (nf = nfb x the plan's batches)
+  uint32_t nfb;  // chunks per scalar vector (nf = nfb x the plan's vectors)
   size_t nmain;  // items: NH * NLO main slots
   size_t ctr_words() const { return (size_t)NH + 16 + (size_t)BS_NSC * NH + 2 * (ITEM_CAP_MAX + 1); }
   uint32_t* ghist(uint32_t* ctr) const { return ctr + NH + 16 + (size_t)BS_NSC * NH; }
@@ -2849,47 +2820,23 @@ static BsGeom bs_geom(const MsmPlan& P, size_t n) {
 constexpr int BS_ST = 4096;  // k_bs_scatter2 entries per LDS sub-tile
 static size_t bs_lds_scatter2(const BsGeom& g) { return rs_scatter_lds(g.NLO, BS_ST, 256) + (2 * (size_t)g.NH + 2) * 4; }
 
-template <int C, bool BAL>
-static void launch_bs_p1(hipStream_t st, const uint32_t* sc, size_t n, int Wp, uint32_t B, uint32_t wsel, const BsGeom& g,
-                         uint32_t* ctr, uint32_t* next_ctr, uint32_t* choff, uint32_t* okey, uint32_t* oval,
-                         bool scatter, bool batch, size_t sstride) {
-  constexpr int W = msm_windows(C);
-  uint32_t* bintot = ctr;
-  uint32_t* sctot = ctr + g.NH + 16;
-  if (batch) {
-    if (scatter)
-      k_bs_scatter1<C, 256, BAL, true><<<g.nf, 256, rs_scatter_lds(g.NH, 256 * W, 256), st>>>(
-          sc, n, Wp, B, wsel, g.NH, g.lob, g.CS, g.scs, bintot, sctot, choff, reinterpret_cast<BsKey*>(okey), oval,
-          g.nfb, sstride);
-    else
-      k_bs_count<C, BAL, true><<<g.nf, 256, g.NH * 4, st>>>(sc, n, Wp, B, wsel, g.NH, g.lob, g.CS, g.scs, bintot,
-                                                            sctot, choff, next_ctr, (uint32_t)g.ctr_words(), g.nfb,
-                                                            sstride);
-    return;
-  }
-  if (scatter)
-    k_bs_scatter1<C, 256, BAL><<<g.nf, 256, rs_scatter_lds(g.NH, 256 * W, 256), st>>>(
-        sc, n, Wp, B, wsel, g.NH, g.lob, g.CS, g.scs, bintot, sctot, choff, reinterpret_cast<BsKey*>(okey), oval);
-  else
-    k_bs_count<C, BAL><<<g.nf, 256, g.NH * 4, st>>>(sc, n, Wp, B, wsel, g.NH, g.lob, g.CS, g.scs, bintot, sctot, choff,
-                                                    next_ctr, (uint32_t)g.ctr_words());
-}
+// bin sort pass 1: the count (scatter = false) or the scatter over the (chunks
+// per vector, vectors) grid
 static int bs_p1(int c, bool bal, hipStream_t st, const uint32_t* sc, size_t n, int Wp, uint32_t B, uint32_t wsel, const BsGeom& g,
                  uint32_t* ctr, uint32_t* next_ctr, uint32_t* choff, uint32_t* okey, uint32_t* oval, bool scatter,
-                 bool batch = false, size_t sstride = 0) {
-  switch (c) {
-#define ZK_C(CC)                                                                                  \
-  case CC:                                                                                        \
-    if (bal) launch_bs_p1<CC, true>(st, sc, n, Wp, B, wsel, g, ctr, next_ctr, choff, okey, oval, scatter, batch, sstride); \
-    else launch_bs_p1<CC, false>(st, sc, n, Wp, B, wsel, g, ctr, next_ctr, choff, okey, oval, scatter, batch, sstride);    \
-    break;
-    ZK_C(12) ZK_C(13) ZK_C(14) ZK_C(15) ZK_C(16) ZK_C(17) ZK_C(18) ZK_C(19) ZK_C(20) ZK_C(21) ZK_C(22)
-#undef ZK_C
-    default:
-      set_error("bin sort: unsupported MSM window %d", c);
-      return ZKMI_EINVAL;
-  }
-  return 0;
+                 uint32_t nb, size_t sstride) {
+  uint32_t* bintot = ctr;
+  uint32_t* sctot = ctr + g.NH + 16;
+  const dim3 grid(g.nfb, nb);
+  return dispatch_window<12>(c, bal, "bin sort: ", [&](auto C, auto BAL) {
+    if (scatter)
+      k_bs_scatter1<C(), 256, BAL()><<<grid, 256, rs_scatter_lds(g.NH, 256 * msm_windows(C()), 256), st>>>(
+          sc, n, Wp, B, wsel, g.NH, g.lob, g.CS, g.scs, bintot, sctot, choff, reinterpret_cast<BsKey*>(okey), oval,
+          sstride);
+    else
+      k_bs_count<C(), BAL()><<<grid, 256, g.NH * 4, st>>>(sc, n, Wp, B, wsel, g.NH, g.lob, g.CS, g.scs, bintot, sctot,
+                                                         choff, next_ctr, (uint32_t)g.ctr_words(), sstride);
+  });
 }
 
 // Timing ablation for development only (tools/headline_loop.py): ZKMI_DEBUG_SKIP
@@ -2992,10 +2939,10 @@ static int msm_sort_phase(zkmi_ctx* ctx, MsmLane* lane, const MsmPlan& P, const 
       io.split = split;
       io.stage = stage;
     }
-    ZK_TRY(bs_p1(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, g, ctr, next_ctr, choff, okey, oval, false, P.batch,
-                 P.sstride));
-    ZK_TRY(bs_p1(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, g, ctr, next_ctr, choff, okey, oval, true, P.batch,
-                 P.sstride));
+    ZK_TRY(bs_p1(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, g, ctr, next_ctr, choff, okey, oval, false,
+                 (uint32_t)P.nb, P.sstride));
+    ZK_TRY(bs_p1(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, g, ctr, next_ctr, choff, okey, oval, true,
+                 (uint32_t)P.nb, P.sstride));
     ZK_HIP(hipEventRecord(lane->consumed, st));
     ZK_HIP(hipStreamWaitEvent(ctx->stream, lane->consumed, 0));
     const uint32_t gt = ((g.T2max + 7) / 8) * 8;  // XCD-mapped grid (rs_xcd_tile)
@@ -3029,8 +2976,8 @@ static int msm_sort_phase(zkmi_ctx* ctx, MsmLane* lane, const MsmPlan& P, const 
       lane->ss_clean_words = P.K;
     }
     lane->ss_clean = nullptr;  // until every kernel of this sort is queued
-    ZK_TRY(small_sort(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, P.K, scnt, scur, bstart, sval,
-                      P.batch ? (uint32_t)P.nb : 0u, P.sstride));
+    ZK_TRY(small_sort(P.c, P.bal, st, d_scalars, n, P.Wp(), P.B, P.wsel, P.K, scnt, scur, bstart, sval, (uint32_t)P.nb,
+                      P.sstride));
     lane->ss_clean = scnt;
     ZK_HIP(hipEventRecord(lane->consumed, st));
     ZK_HIP(hipStreamWaitEvent(ctx->stream, lane->consumed, 0));
@@ -3047,8 +2994,8 @@ static int msm_sort_phase(zkmi_ctx* ctx, MsmLane* lane, const MsmPlan& P, const 
   ZK_TRY(ws.get("msm_bsums", ((std::max(len1, len2) + 1023) / 1024) * 4 + 16, (void**)&bsums));
   ZK_TRY(ws.get("msm_tot", 64, (void**)&tot));
   {
-    ZK_TRY(dispatch_digits(P.c, st, d_scalars, n, P.p, P.batch ? P.Wp() : P.W, P.bal, digits,
-                           P.batch ? (uint32_t)P.nb : 0u, P.sstride));
+    // (no wsel here: window-sharded plans have c >= 12, so Wp() is W / nb)
+    ZK_TRY(dispatch_digits(P.c, st, d_scalars, n, P.p, P.Wp(), P.bal, digits, (uint32_t)P.nb, P.sstride));
     ZK_HIP(hipEventRecord(lane->consumed, st));
     ZK_HIP(hipStreamWaitEvent(ctx->stream, lane->consumed, 0));
   }
@@ -3427,38 +3374,44 @@ int msm_submit(zkmi_ctx* ctx, const zkmi_bases* b, size_t offset, const void* d_
   return rc;
 }
 
-// k MSMs with the same scalars (and range) over k base sets: one digits +
-// sort pass, then one accumulation per set, all on one lane.  Base sets whose
-// window plan differs from the first one's get their own sort.
+// The same nb scalar vectors (n > 0 scalars each, sstride words apart) over k
+// base sets: one digits + sort pass on the next lane, then one accumulation
+// per set with the same plan; base sets whose window plan differs from the
+// first one's get their own sort.  own(j, P) makes set j's job for plan P and
+// hands it to whoever frees the jobs, before its accumulation is queued.
+template <class Own>
+static int msm_sort_acc_shared(zkmi_ctx* ctx, const zkmi_bases* const* bs, int k, size_t offset, const uint32_t* sc,
+                               size_t n, int nb, size_t sstride, Own own) {
+  std::vector<bool> done(k, false);
+  for (int i = 0; i < k; i++) {
+    if (done[i]) continue;
+    const MsmPlan P = msm_plan_batch(ctx, bs[i], n, nb, sstride);
+    ZK_TRY(check_size(P, n));
+    MsmLane* lane = nullptr;
+    ZK_TRY(get_lane(ctx, &lane));
+    uint32_t *sval, *bstart;
+    ZK_TRY(msm_sort_phase(ctx, lane, P, sc, n, &sval, &bstart));
+    for (int j = i; j < k; j++) {
+      if (done[j] || (j > i && !same_plan(P, msm_plan_batch(ctx, bs[j], n, nb, sstride)))) continue;
+      zkmi_msm_job* job = own(j, P);
+      done[j] = true;
+      ZK_TRY(msm_acc_any(ctx, lane, P, bs[j], offset, n, sval, bstart, job));
+    }
+  }
+  return 0;
+}
+
+// k MSMs with the same scalars (and range) over k base sets (msm_sort_acc_shared)
 int msm_submit_shared(zkmi_ctx* ctx, const zkmi_bases* const* bs, int k, size_t offset, const void* d_scalars,
                       size_t n, zkmi_msm_job** jobs) {
   for (int i = 0; i < k; i++) jobs[i] = nullptr;
   for (int i = 0; i < k; i++) ZK_TRY(check_range(bs[i], offset, n));
-  int rc = 0;
-  MsmLane* lane = nullptr;
-  std::vector<bool> done(k, false);
-  for (int i = 0; i < k && !rc; i++) {
-    if (done[i]) continue;
-    const MsmPlan P = msm_plan(ctx, bs[i], n);
-    jobs[i] = new_job(ctx, bs[i], P, n);
-    done[i] = true;
-    if (n == 0) {
-      for (int j = i + 1; j < k; j++)
-        if (!done[j]) jobs[j] = new_job(ctx, bs[j], msm_plan(ctx, bs[j], n), n), done[j] = true;
-      break;
-    }
-    if ((rc = check_size(P, n))) break;
-    if ((rc = get_lane(ctx, &lane))) break;
-    uint32_t *sval, *bstart;
-    if ((rc = msm_sort_phase(ctx, lane, P, (const uint32_t*)d_scalars, n, &sval, &bstart))) break;
-    if ((rc = msm_acc_any(ctx, lane, P, bs[i], offset, n, sval, bstart, jobs[i]))) break;
-    for (int j = i + 1; j < k && !rc; j++) {
-      if (done[j] || !same_plan(P, msm_plan(ctx, bs[j], n))) continue;
-      jobs[j] = new_job(ctx, bs[j], P, n);
-      done[j] = true;
-      rc = msm_acc_any(ctx, lane, P, bs[j], offset, n, sval, bstart, jobs[j]);
-    }
+  if (n == 0) {
+    for (int i = 0; i < k; i++) jobs[i] = new_job(ctx, bs[i], msm_plan(ctx, bs[i], n), n);
+    return 0;
   }
+  const int rc = msm_sort_acc_shared(ctx, bs, k, offset, (const uint32_t*)d_scalars, n, 1, 0,
+                                     [&](int j, const MsmPlan& P) { return jobs[j] = new_job(ctx, bs[j], P, n); });
   if (rc) {
     for (int i = 0; i < k; i++) {
       msm_job_free(jobs[i]);
@@ -3632,8 +3585,8 @@ int msm_device(zkmi_ctx* ctx, const zkmi_bases* b, size_t offset, const void* d_
 // nb scalar vectors over one base set and range (zkmi_msm_batch_submit): the
 // vectors are split into groups of at most G; a group is ONE launch sequence
 // over the plan msm_plan_batch makes of it, on the next lane, so groups
-// pipeline the way consecutive MSMs do.  A group of one runs the single-MSM
-// path as it is.
+// pipeline the way consecutive MSMs do.  A group of one is the single MSM's
+// plan and launches.
 //
 // Group size: zkmi_ctx_set_batch_group, or BATCH_GROUP_AUTO; then the largest
 // g <= that for which the batched plan keeps K' <= BATCH_K_MAX buckets and
@@ -3680,25 +3633,13 @@ int msm_batch_submit_shared(zkmi_ctx* ctx, const zkmi_bases* const* bs, int k, s
   int rc = 0;
   for (size_t b0 = 0; b0 < nb && !rc; b0 += (size_t)G) {
     const int gb = (int)std::min<size_t>((size_t)G, nb - b0);
-    const uint32_t* sc = (const uint32_t*)d_scalars + b0 * sstride;
-    MsmLane* lane = nullptr;
-    std::vector<bool> done(k, false);
-    for (int i = 0; i < k && !rc; i++) {
-      if (done[i]) continue;
-      const MsmPlan P = gb > 1 ? msm_plan_batch(ctx, bs[i], n, gb, sstride) : msm_plan(ctx, bs[i], n);
-      if ((rc = check_size(P, n))) break;
-      if ((rc = get_lane(ctx, &lane))) break;
-      uint32_t *sval, *bstart;
-      if ((rc = msm_sort_phase(ctx, lane, P, sc, n, &sval, &bstart))) break;
-      for (int j = i; j < k && !rc; j++) {
-        if (done[j] || (j > i && !same_plan(msm_plan(ctx, bs[i], n), msm_plan(ctx, bs[j], n)))) continue;
-        zkmi_msm_job* part = new_job(ctx, bs[j], P, n);
-        part->nbat = gb;
-        jobs[j]->parts.push_back(part);  // owned from here on, whatever follows
-        done[j] = true;
-        rc = msm_acc_any(ctx, lane, P, bs[j], offset, n, sval, bstart, part);
-      }
-    }
+    rc = msm_sort_acc_shared(ctx, bs, k, offset, (const uint32_t*)d_scalars + b0 * sstride, n, gb, sstride,
+                             [&](int j, const MsmPlan& P) {
+                               zkmi_msm_job* part = new_job(ctx, bs[j], P, n);
+                               part->nbat = gb;
+                               jobs[j]->parts.push_back(part);  // owned from here on, whatever follows
+                               return part;
+                             });
   }
   if (rc) {
     for (int i = 0; i < k; i++) {

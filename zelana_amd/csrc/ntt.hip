@@ -342,23 +342,21 @@ __device__ __forceinline__ Fe ntt_tab_scale(Fe v, uint64_t i, const NttIo& io) {
 // 1024-element tiles in radix-4 rounds (36 KB LDS, <= 128 VGPRs: 4 waves/SIMD
 // to hide the load and twiddle latency the 2-wave form exposes).
 
-// BAT (batched transforms, ntt_batch_*): blockIdx.y selects the vector; vector
-// v of src / dst starts v * sstr / v * dstr words after the first.  Twiddles,
-// the group plan and the coset tables are shared.
+// blockIdx.y selects the vector (batched transforms, ntt_batch_*; one row for
+// a single transform): vector v of src / dst starts v * sstr / v * dstr words
+// after the first.  Twiddles, the group plan and the coset tables are shared.
 struct NttBatch {
   size_t sstr, dstr;
 };
-template <bool DIT, int PRO, int EPI, bool PERM, int TB, int RB, bool BAT = false>
+template <bool DIT, int PRO, int EPI, bool PERM, int TB, int RB>
 __global__ void __launch_bounds__(1 << (TB - RB), (RB == 3 ? 2 : 4) * 256 / (1 << (TB - RB))) k_ntt_group(const uint32_t* src, uint32_t* dst,
                                                                           const uint32_t* __restrict__ tw, uint32_t logn,
                                                                           uint32_t a, uint32_t k, NttIo io,
-                                                                          NttBatch bat = NttBatch{0, 0}) {
+                                                                          NttBatch bat) {
   constexpr int TILE = 1 << TB, EPT = 1 << RB;
   extern __shared__ __align__(16) uint32_t lds[];  // [limb][slot]
-  if (BAT) {
-    src += (size_t)blockIdx.y * bat.sstr;
-    dst += (size_t)blockIdx.y * bat.dstr;
-  }
+  src += (size_t)blockIdx.y * bat.sstr;
+  dst += (size_t)blockIdx.y * bat.dstr;
   NttGroup g;
   g.logn = logn;
   g.a = a;
@@ -644,32 +642,28 @@ static std::vector<uint32_t> ntt_groups(uint32_t logn) {
 #define ZK_NTT_TB_OUTER 10
 #endif
 static_assert(!ZK_NTT_TW_L8P || ZK_NTT_TB_OUTER == 10, "the limb-8 layout assumes 1024-element outer tiles");
-// nb = 0: one vector (the launch of before); nb >= 1: nb vectors, bat words apart
+// nb >= 1 vectors, bat words apart: the 1024-element tile shape, one grid row
+// per vector
 template <bool DIT, int PRO, int EPI, bool PERM>
 static void launch_group(hipStream_t st, const uint32_t* src, uint32_t* dst, const uint32_t* tw, uint32_t logn,
-                         uint32_t a, uint32_t k, const NttIo& io, unsigned nb = 0, NttBatch bat = NttBatch{0, 0}) {
+                         uint32_t a, uint32_t k, const NttIo& io, unsigned nb, NttBatch bat) {
   constexpr int TBo = ZK_NTT_TB_OUTER;
-  if (nb) {  // batched: the 1024-element tile shape, one grid row per vector
-    const size_t sm = (size_t)1024 * NL * 4;
-    const dim3 grid((unsigned)((1ull << logn) / 1024), nb);
-    k_ntt_group<DIT, PRO, EPI, PERM, 10, 2, true><<<grid, 256, sm, st>>>(src, dst, tw, logn, a, k, io, bat);
-    return;
-  }
-  if (TBo != 10 && !PERM && a > k && logn >= (uint32_t)TBo && k <= (uint32_t)TBo - 2) {  // a pass with column bits
+  // (development builds only: the big outer tile, for one vector)
+  if (TBo != 10 && nb == 1 && !PERM && a > k && logn >= (uint32_t)TBo && k <= (uint32_t)TBo - 2) {  // a pass with column bits
     const size_t sm = ((size_t)1 << TBo) * NL * 4;
     const unsigned grid = (unsigned)((1ull << logn) >> TBo);
-    k_ntt_group<DIT, PRO, EPI, PERM, TBo, 2><<<grid, 1 << (TBo - 2), sm, st>>>(src, dst, tw, logn, a, k, io);
+    k_ntt_group<DIT, PRO, EPI, PERM, TBo, 2><<<grid, 1 << (TBo - 2), sm, st>>>(src, dst, tw, logn, a, k, io, bat);
     return;
   }
   const size_t sm = (size_t)1024 * NL * 4;
-  const unsigned grid = (unsigned)((1ull << logn) / 1024);
-  k_ntt_group<DIT, PRO, EPI, PERM, 10, 2><<<grid, 256, sm, st>>>(src, dst, tw, logn, a, k, io);
+  const dim3 grid((unsigned)((1ull << logn) / 1024), nb);
+  k_ntt_group<DIT, PRO, EPI, PERM, 10, 2><<<grid, 256, sm, st>>>(src, dst, tw, logn, a, k, io, bat);
 }
 
 // in-place transform in the requested order without scaling:
 // dit=false: natural in -> bit-reversed out; dit=true: bit-reversed in -> natural out
 // epi (DIF only): 0 none, 2 = x * lo[i] * hi[i] at natural index i, canonical out
-// nb = 0: one vector; nb >= 1: the batched launches over nb vectors vstr words apart
+// nb >= 1 vectors vstr words apart, one launch sequence
 int ntt_raw_epi_n(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, int epi, const uint32_t* lo,
                   const uint32_t* hi, unsigned nb, size_t vstr) {
   const uint32_t* tw;
@@ -679,13 +673,12 @@ int ntt_raw_epi_n(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, 
   if ((1u << logn) < (uint32_t)NTT_TILE && logn < 11) {
     size_t sm = ((size_t)1 << logn) * NL * 4;
     ScopedKernelTimer tm(ctx, "ntt_small");
-    const unsigned gy = nb ? nb : 1;
-    if (dit) k_ntt_small<true><<<dim3(1, gy), 256, sm, st>>>(d, tw, logn, vstr);
-    else k_ntt_small<false><<<dim3(1, gy), 256, sm, st>>>(d, tw, logn, vstr);
+    if (dit) k_ntt_small<true><<<dim3(1, nb), 256, sm, st>>>(d, tw, logn, vstr);
+    else k_ntt_small<false><<<dim3(1, nb), 256, sm, st>>>(d, tw, logn, vstr);
     ZK_HIP(hipGetLastError());
     if (epi) {
       ScopedKernelTimer tm2(ctx, "ntt_scale");
-      k_scale_rev_small<<<dim3((unsigned)(((1ull << logn) + 255) / 256), gy), 256, 0, st>>>(d, logn, lo, hi, vstr);
+      k_scale_rev_small<<<dim3((unsigned)(((1ull << logn) + 255) / 256), nb), 256, 0, st>>>(d, logn, lo, hi, vstr);
       ZK_HIP(hipGetLastError());
     }
     return 0;
@@ -715,30 +708,29 @@ int ntt_raw_epi_n(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, 
 }
 int ntt_raw_epi(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit, int epi, const uint32_t* lo,
                 const uint32_t* hi) {
-  return ntt_raw_epi_n(ctx, d, logn, inv, dit, epi, lo, hi, 0, 0);
+  return ntt_raw_epi_n(ctx, d, logn, inv, dit, epi, lo, hi, 1, 0);
 }
 int ntt_raw(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inv, bool dit) {
   return ntt_raw_epi(ctx, d, logn, inv, dit, 0, nullptr, nullptr);
 }
 
 // in-place permutation natural <-> bit-reversed (+ optional scaling, + full reduction)
-static int ntt_bitrev_scaled(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, BitrevScale sc, unsigned nb = 0,
+static int ntt_bitrev_scaled(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, BitrevScale sc, unsigned nb = 1,
                              size_t vstr = 0) {
   hipStream_t st = ctx->stream;
   ScopedKernelTimer tm(ctx, "ntt_bitrev");
-  const unsigned gy = nb ? nb : 1;
   if (logn >= 10) {
     uint32_t b = 5;
     unsigned grid = 1u << (logn - 2 * b);
-    k_bitrev_tiled<<<dim3(grid, gy), 256, 2 * (1u << (2 * b)) * 32, st>>>(d, logn, b, sc, vstr);
+    k_bitrev_tiled<<<dim3(grid, nb), 256, 2 * (1u << (2 * b)) * 32, st>>>(d, logn, b, sc, vstr);
   } else {
     uint32_t* tmp;
     const size_t vb = ((size_t)1 << logn) * 32;
-    ZK_TRY(ctx->ws.get("ntt_tmp_small", gy * vb, (void**)&tmp));
-    k_bitrev_naive<<<dim3(((1u << logn) + 255) / 256, gy), 256, 0, st>>>(d, tmp, logn, sc, vstr);
-    // (batched: the packed scratch vectors back to their strided places; the
-    // bytes between two vectors are not written)
-    if (nb) ZK_HIP(hipMemcpy2DAsync(d, vstr * 4, tmp, vb, vb, nb, hipMemcpyDeviceToDevice, st));
+    ZK_TRY(ctx->ws.get("ntt_tmp_small", nb * vb, (void**)&tmp));
+    k_bitrev_naive<<<dim3(((1u << logn) + 255) / 256, nb), 256, 0, st>>>(d, tmp, logn, sc, vstr);
+    // (the packed scratch vectors back to their strided places; the bytes
+    // between two vectors are not written.  One vector: the plain copy.)
+    if (nb > 1) ZK_HIP(hipMemcpy2DAsync(d, vstr * 4, tmp, vb, vb, nb, hipMemcpyDeviceToDevice, st));
     else ZK_HIP(hipMemcpyAsync(d, tmp, vb, hipMemcpyDeviceToDevice, st));
   }
   ZK_HIP(hipGetLastError());
@@ -757,10 +749,10 @@ int ntt_bitrev(zkmi_ctx* ctx, uint32_t* d, uint32_t logn) {
 // Small transforms (one tile or less) keep the single-workgroup kernel and
 // a separate bit reversal.
 int ntt_device(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inverse, int coset) {
-  return ntt_device_n(ctx, d, logn, inverse, coset, 0, 0);
+  return ntt_device_n(ctx, d, logn, inverse, coset, 1, 0);
 }
-// nb = 0: one vector; nb >= 1: nb vectors vstr words apart, one launch
-// sequence (the scratch of the out-of-place passes holds nb packed vectors)
+// nb >= 1 vectors vstr words apart, one launch sequence (the scratch of the
+// out-of-place passes holds nb packed vectors)
 int ntt_device_n(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inverse, int coset, unsigned nb, size_t vstr) {
   if (logn > 28) {
     set_error("ntt: log_n %u > 28 (two-adicity of Fr)", logn);
@@ -772,7 +764,7 @@ int ntt_device_n(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inverse, int cos
     if (!inverse) {
       if (coset) {
         ScopedKernelTimer tm(ctx, "ntt_scale");
-        k_ntt_coset_scale<<<dim3((unsigned)(((1ull << logn) + 255) / 256), nb ? nb : 1), 256, 0, ctx->stream>>>(
+        k_ntt_coset_scale<<<dim3((unsigned)(((1ull << logn) + 255) / 256), nb), 256, 0, ctx->stream>>>(
             d, logn, dc.lo_g, dc.hi_gf, vstr);
         ZK_HIP(hipGetLastError());
       }
@@ -787,7 +779,7 @@ int ntt_device_n(zkmi_ctx* ctx, uint32_t* d, uint32_t logn, int inverse, int cos
   ZK_TRY(get_twiddles(ctx, logn, inverse, &tw));
   uint32_t* s;
   const size_t vw = ((size_t)1 << logn) * 8;  // words of a packed vector
-  ZK_TRY(ctx->ws.get("ntt_scratch", (nb ? nb : 1) * vw * 4, (void**)&s));
+  ZK_TRY(ctx->ws.get("ntt_scratch", nb * vw * 4, (void**)&s));
   hipStream_t st = ctx->stream;
   const std::vector<uint32_t> ks = ntt_groups(logn);
   const int ng = (int)ks.size();

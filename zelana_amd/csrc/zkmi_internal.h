@@ -265,8 +265,8 @@ int scalars_generate(zkmi_ctx* ctx, uint64_t seed, size_t first, size_t n, void*
 
 // NTT entry (ntt.hip): in-place on device, natural order
 int ntt_device(zkmi_ctx* ctx, uint32_t* d_data, uint32_t log_n, int inverse, int coset);
-// nb >= 1 vectors, vstr u32 words apart, in one launch sequence (nb = 0: the
-// single-vector launches of ntt_device)
+// nb >= 1 vectors, vstr u32 words apart, in one launch sequence (ntt_device
+// is nb = 1)
 int ntt_device_n(zkmi_ctx* ctx, uint32_t* d_data, uint32_t log_n, int inverse, int coset, unsigned nb, size_t vstr);
 // per-log_n NTT domain tables (Montgomery): g^x = lo[x mod 2^KB] * hi[x >> KB]
 constexpr uint32_t COSET_KB = 14;
