@@ -482,6 +482,47 @@ int zkmi_batch_inputs_alt_bn128(const uint8_t roots[6 * 32], uint64_t batch_id, 
  * the forge's <= 7-point Lagrange sums (:252-290) */
 int zkmi_g1_mul(const uint64_t p[8], const uint64_t k[4], uint64_t out[8]);
 
+/* ------------------------------------------------- batched verification
+ * zkmi_groth16_verify for nb proofs under one key, with the Miller loops on
+ * the GPU.  With weights rho_i (non-zero, 128 bits)
+ *   prod_i e(rho_i A_i, B_i) e(-(sum rho_i) alpha, beta)
+ *     e(-sum rho_i X_i, gamma) e(-sum rho_i C_i, delta) = 1
+ * is nb + 3 Miller loops (one GPU lane each, two kernels on the context
+ * stream: no new stream) and ONE final exponentiation on the host.  If it
+ * holds, every proof that passed point validation is valid.  If not, the host
+ * bisects over the per-proof Miller values: a probe is a subset product, the
+ * subset's three fixed pairs and one final exponentiation, at most two probes
+ * a level; a subset of one is decided exactly.  A valid proof is never
+ * rejected; an invalid one is accepted with probability about 2^-127 over the
+ * weights.  Worst case: every proof bad costs about 2 nb probes, slower than
+ * a loop of zkmi_groth16_verify (a batch is expected to be mostly valid). */
+typedef struct zkmi_vk zkmi_vk;
+/* arkworks-compressed VerifyingKey, decoded and validated once (as
+ * zkmi_groth16_verify does per call); ZKMI_EPOINT for a bad key */
+int zkmi_vk_load(zkmi_ctx* ctx, const uint8_t* bytes, size_t len, zkmi_vk** out);
+void zkmi_vk_destroy(zkmi_vk* vk); /* before the context, like keys and base sets */
+int zkmi_vk_info(const zkmi_vk* vk, uint64_t out[1]); /* [n_inputs] */
+/* pairs: Miller loops run on the GPU (nb + 3); final_exps: host final
+ * exponentiations (1 when every proof is valid); invalid_points: proofs that
+ * failed point validation */
+typedef struct {
+  uint64_t pairs;
+  uint64_t final_exps;
+  uint64_t invalid_points;
+} zkmi_verify_stats;
+/* valid[i] = what zkmi_groth16_verify returns for proof i (up to the
+ * soundness error above).  inputs: nb x n_inputs x 4 u64, each < r (else
+ * ZKMI_EINVAL for the whole call); a bad proof point is valid[i] = 0, not an
+ * error.  nb = 0 is valid and launches nothing.  Synchronous.
+ * rho: NULL = the library draws the weights from the OS (getrandom) inside
+ * the call, after the proofs are fixed -- the only sound use: a prover who
+ * knows the weights before choosing its proofs can make invalid proofs cancel
+ * in the combined check.  Non-NULL rho (nb x 2 u64, each 128-bit value
+ * non-zero, else ZKMI_EINVAL) exists for reproducible tests only. */
+int zkmi_groth16_verify_many(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const uint64_t* a,
+                             const uint64_t* b, const uint64_t* c, const uint64_t* rho, uint8_t* valid,
+                             zkmi_verify_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,11 @@ class R1CSStatusStruct(ctypes.Structure):
 ROW_NONE = 2**64 - 1  # ZKMI_ROW_NONE
 
 
+class VerifyStatsStruct(ctypes.Structure):
+    """zkmi_verify_stats"""
+    _fields_ = [("pairs", ctypes.c_uint64), ("final_exps", ctypes.c_uint64), ("invalid_points", ctypes.c_uint64)]
+
+
 # (name, restype, argtypes) — every symbol declared in include/zkmi.h
 SIGNATURES = [
     ("zkmi_last_error", ctypes.c_char_p, []),
@@ -141,6 +146,11 @@ SIGNATURES = [
     ("zkmi_proof_to_alt_bn128_bytes", ctypes.c_int, [u64p, u64p, u64p, u8p]),
     ("zkmi_batch_inputs_alt_bn128", ctypes.c_int, [u8p, ctypes.c_uint64, u8p]),
     ("zkmi_g1_mul", ctypes.c_int, [u64p, u64p, u64p]),
+    ("zkmi_vk_load", ctypes.c_int, [vp, u8p, sz, ctypes.POINTER(vp)]),
+    ("zkmi_vk_destroy", None, [vp]),
+    ("zkmi_vk_info", ctypes.c_int, [vp, u64p]),
+    ("zkmi_groth16_verify_many", ctypes.c_int, [vp, vp, sz, u64p, u64p, u64p, u64p, u64p, u8p,
+                                                ctypes.POINTER(VerifyStatsStruct)]),
     ("zkmi_proof_to_solana_bytes", ctypes.c_int, [u64p, u64p, u64p, u8p]),
     ("zkmi_proof_serialize_compressed", ctypes.c_int, [u64p, u64p, u64p, u8p]),
 ]

@@ -29,12 +29,13 @@
 
 #include "../../include/zkmi.h"
 #include "host_field.h"
+#include "verify_internal.h"
 
 namespace zk {
 void set_error(const char* fmt, ...);
 }
 
-namespace {
+namespace zkv {
 
 using namespace zkh;
 
@@ -131,14 +132,6 @@ bool fq2_sqrt(const F2& a, F2* out) {
 }
 
 // ------------------------------------------------------------- points
-struct G1 {
-  F4 x, y;
-  bool inf;
-};
-struct G2 {
-  F2 x, y;
-  bool inf;
-};
 bool g1_on_curve(const G1& p) {
   if (p.inf) return true;
   return feq(fmul(p.y, p.y), fadd(fmul(fmul(p.x, p.x), p.x), fsmall(3)));
@@ -279,9 +272,6 @@ bool g2_decompress(const uint8_t in[64], G2* out) {
 }
 
 // ------------------------------------------------------------- Fq12
-struct F12 {
-  F4 c[12];
-};
 F12 f12_one() {
   F12 r;
   memset(&r, 0, sizeof(r));
@@ -400,12 +390,13 @@ struct Jac {
   bool inf;
 };
 
-// prod_k e(P_k, Q_k) == 1  (reduced Tate pairing)
-bool pairing_product_is_one(const std::vector<G1>& ps, const std::vector<G2>& qs) {
+// Miller value of prod_k e(P_k, Q_k)  (reduced Tate pairing, before the final
+// exponentiation)
+F12 miller_value(const std::vector<G1>& ps, const std::vector<G2>& qs) {
   std::vector<size_t> idx;
   for (size_t k = 0; k < ps.size(); k++)
     if (!ps[k].inf && !qs[k].inf) idx.push_back(k);
-  if (idx.empty()) return true;
+  if (idx.empty()) return f12_one();
   std::vector<Jac> T(ps.size());
   std::vector<QUn> Q(ps.size());
   for (size_t k : idx) {
@@ -461,7 +452,10 @@ bool pairing_product_is_one(const std::vector<G1>& ps, const std::vector<G2>& qs
       }
     }
   }
-  // final exponentiation: h = (f^(q^2) f)^((q^4 - q^2 + 1)/r) must lie in Fq6
+  return f;
+}
+// final exponentiation: h = (f^(q^2) f)^((q^4 - q^2 + 1)/r) must lie in Fq6
+bool final_exp_is_one(const F12& f) {
   F12 h = f12_pow(f12_mul(f12_frob2(f), f), HARD, 12);
   bool nonzero = false;
   for (int i = 0; i < 12; i++) nonzero |= !fzero(h.c[i]);
@@ -469,6 +463,10 @@ bool pairing_product_is_one(const std::vector<G1>& ps, const std::vector<G2>& qs
   for (int i = 1; i < 12; i += 2)
     if (!fzero(h.c[i])) return false;
   return true;
+}
+// prod_k e(P_k, Q_k) == 1
+bool pairing_product_is_one(const std::vector<G1>& ps, const std::vector<G2>& qs) {
+  return final_exp_is_one(miller_value(ps, qs));
 }
 
 // ------------------------------------------------------------- encodings
@@ -528,11 +526,6 @@ void g2_to_be(uint8_t o[128], const G2& p) {
 
 // arkworks-compressed VerifyingKey<Bn254>: alpha(32) beta(64) gamma(64)
 // delta(64) u64-LE count + IC x 32 (prover/l2_vk.json layout)
-struct Vk {
-  G1 alpha;
-  G2 beta, gamma, delta;
-  std::vector<G1> ic;
-};
 bool vk_decode(const uint8_t* b, size_t len, Vk* vk, const char** why) {
   if (len < 232) {
     *why = "verifying key shorter than 232 bytes";
@@ -558,8 +551,180 @@ bool vk_decode(const uint8_t* b, size_t len, Vk* vk, const char** why) {
   return true;
 }
 
+G1 g1_neg(G1 p) {
+  if (!p.inf) p.y = fneg(p.y);
+  return p;
+}
+void g2_to_canon(uint64_t o[16], const G2& p) {
+  if (p.inf) {
+    memset(o, 0, 128);
+    return;
+  }
+  to_canon(o, p.x.c0);
+  to_canon(o + 4, p.x.c1);
+  to_canon(o + 8, p.y.c0);
+  to_canon(o + 12, p.y.c1);
+}
+G1 g1_sum(const G1* pts, const size_t* idx, size_t n) {
+  zk::Xyzz<HFq> acc = zk::xyzz_inf<HFq>();
+  for (size_t k = 0; k < n; k++) {
+    const G1& p = pts[idx[k]];
+    if (p.inf) continue;
+    zk::Aff<HFq> a;
+    a.x = p.x;
+    a.y = p.y;
+    acc = zk::xyzz_madd(acc, a);
+  }
+  G1 r;
+  r.inf = !xyzz_to_aff<HFq>(acc, &r.x, &r.y);
+  return r;
+}
+F12 f12_from_canon(const uint64_t c[48]) {
+  F12 r;
+  for (int i = 0; i < 12; i++) r.c[i] = from_canon(c + 4 * i);
+  return r;
+}
+void f12_to_canon(uint64_t c[48], const F12& a) {
+  for (int i = 0; i < 12; i++) to_canon(c + 4 * i, a.c[i]);
+}
+
+// ------------------------------------------------- batched verification
+// (sum of 128 x 256-bit products) mod r, by plain long arithmetic: the sums
+// are a few hundred word operations per public input, far off any hot path
+struct Wide {
+  uint64_t w[8];
+};
+void wide_mac(Wide& acc, const uint64_t a[2], const uint64_t b[4]) {
+  for (int i = 0; i < 2; i++) {
+    uint64_t c = 0;
+    for (int j = 0; j < 4; j++) {
+      u128 t = (u128)a[i] * b[j] + acc.w[i + j] + c;
+      acc.w[i + j] = (uint64_t)t;
+      c = (uint64_t)(t >> 64);
+    }
+    for (int k = i + 4; c && k < 8; k++) {
+      u128 t = (u128)acc.w[k] + c;
+      acc.w[k] = (uint64_t)t;
+      c = (uint64_t)(t >> 64);
+    }
+  }
+}
+void wide_mod_r(uint64_t out[4], const Wide& a) {
+  uint64_t rem[4] = {0, 0, 0, 0};
+  for (int bit = 511; bit >= 0; bit--) {
+    // rem < r < 2^254, so the shifted value fits four words
+    for (int i = 3; i > 0; i--) rem[i] = (rem[i] << 1) | (rem[i - 1] >> 63);
+    rem[0] = (rem[0] << 1) | ((a.w[bit / 64] >> (bit % 64)) & 1);
+    if (geq(rem, RP)) sub4(rem, rem, RP);
+  }
+  memcpy(out, rem, 32);
+}
+
+int verify_many_check_scalars(size_t nb, size_t n_inputs, const uint64_t* inputs, const uint64_t* rho) {
+  for (size_t i = 0; i < nb; i++) {
+    if ((rho[2 * i] | rho[2 * i + 1]) == 0) {
+      zk::set_error("zkmi_groth16_verify_many: weight %zu is zero", i);
+      return ZKMI_EINVAL;
+    }
+    for (size_t j = 0; j < n_inputs; j++)
+      if (geq(inputs + 4 * (i * n_inputs + j), RP)) {
+        zk::set_error("zkmi_groth16_verify_many: public input %zu of proof %zu not reduced mod r", j, i);
+        return ZKMI_EINVAL;
+      }
+  }
+  return 0;
+}
+
+void verify_many_fixed_g1(const VerifyManyIn& in, const size_t* idx, size_t n, G1 out[3]) {
+  const uint64_t one[4] = {1, 0, 0, 0};
+  uint64_t k[4];
+  Wide s;
+  memset(&s, 0, sizeof(s));
+  for (size_t t = 0; t < n; t++) wide_mac(s, in.rho + 2 * idx[t], one);
+  wide_mod_r(k, s);
+  out[0] = g1_neg(g1_mul(in.vk->alpha, k));
+  G1 x = g1_mul(in.vk->ic[0], k);  // (sum rho_i) IC[0]
+  for (size_t j = 0; j < in.n_inputs; j++) {
+    memset(&s, 0, sizeof(s));
+    for (size_t t = 0; t < n; t++) wide_mac(s, in.rho + 2 * idx[t], in.inputs + 4 * (idx[t] * in.n_inputs + j));
+    wide_mod_r(k, s);
+    x = g1_add(x, g1_mul(in.vk->ic[j + 1], k));  // (sum_i rho_i x_ij) IC[j+1]
+  }
+  out[1] = g1_neg(x);
+  out[2] = g1_neg(g1_sum(in.rc, idx, n));
+}
+
+namespace {
+struct Bisect {
+  const VerifyManyIn& in;
+  uint8_t* valid;
+  uint64_t probes = 0;
+  // does the subset's combined check hold?  (subset product of the per-proof
+  // Miller values, the subset's three fixed pairs on the host, one final
+  // exponentiation)
+  bool probe(const size_t* idx, size_t n) {
+    G1 g[3];
+    verify_many_fixed_g1(in, idx, n, g);
+    F12 f = miller_value({g[0], g[1], g[2]}, {in.vk->beta, in.vk->gamma, in.vk->delta});
+    for (size_t t = 0; t < n; t++) f = f12_mul(f, in.f[idx[t]]);
+    probes++;
+    return final_exp_is_one(f);
+  }
+  // known_fail: the subset is already known not to pass.  Returns whether it
+  // passed.  A subset of one is exact: rho_i is invertible mod r.
+  bool solve(const size_t* idx, size_t n, bool known_fail) {
+    if (n == 0) return true;
+    if (!known_fail && probe(idx, n)) {
+      for (size_t t = 0; t < n; t++) valid[idx[t]] = 1;
+      return true;
+    }
+    if (n == 1) {
+      valid[idx[0]] = 0;
+      return false;
+    }
+    const size_t h = n / 2;
+    const bool left = solve(idx, h, false);
+    solve(idx + h, n - h, left);  // the left half passed: the right one holds the failure
+    return false;
+  }
+};
 }  // namespace
 
+int verify_many_combine(const VerifyManyIn& in, const F12* fixed_all, uint8_t* valid, zkmi_verify_stats* st) {
+  if (in.vk->ic.size() != in.n_inputs + 1) {
+    zk::set_error("zkmi_groth16_verify_many: %zu public inputs for a key with %zu IC points", in.n_inputs,
+                  in.vk->ic.size());
+    return ZKMI_EINVAL;
+  }
+  int rc = verify_many_check_scalars(in.nb, in.n_inputs, in.inputs, in.rho);
+  if (rc) return rc;
+  std::vector<size_t> idx;
+  for (size_t i = 0; i < in.nb; i++) {
+    valid[i] = 0;
+    if (!in.bad[i]) idx.push_back(i);
+  }
+  if (st) st->invalid_points += in.nb - idx.size();
+  if (idx.empty()) return 0;
+  Bisect bs{in, valid};
+  bool all;
+  if (fixed_all) {
+    F12 f = *fixed_all;
+    for (size_t i : idx) f = f12_mul(f, in.f[i]);
+    bs.probes++;
+    all = final_exp_is_one(f);
+  } else {
+    all = bs.probe(idx.data(), idx.size());
+  }
+  if (all)
+    for (size_t i : idx) valid[i] = 1;
+  else
+    bs.solve(idx.data(), idx.size(), true);
+  if (st) st->final_exps += bs.probes;
+  return 0;
+}
+}  // namespace zkv
+
+using namespace zkv;
 using zk::set_error;
 
 extern "C" {

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import ROW_NONE, R1CSStatusStruct, R1CSStruct, ZkmiError, check, lib, u64p, u8p, vp
+from ._lib import ROW_NONE, R1CSStatusStruct, R1CSStruct, VerifyStatsStruct, ZkmiError, check, lib, u64p, u8p, vp
 
 
 def _p64(a: np.ndarray):
@@ -544,6 +544,61 @@ def groth16_verify(vk_bytes: bytes, public_inputs, a, b, c) -> bool:
                                     _p64(np.ascontiguousarray(a, np.uint64)), _p64(np.ascontiguousarray(b, np.uint64)),
                                     _p64(np.ascontiguousarray(c, np.uint64)), ctypes.byref(ok)), "zkmi_groth16_verify")
     return bool(ok.value)
+
+
+class VerifyingKey:
+    """arkworks-compressed VerifyingKey decoded and validated once
+    (zkmi_vk_load), for groth16_verify_many.  A bad key raises ZkmiError."""
+
+    def __init__(self, ctx: Context, vk_bytes: bytes):
+        self.ctx = ctx
+        self.h = vp()
+        ctx._track(self)
+        buf = np.frombuffer(bytes(vk_bytes), np.uint8)
+        check(lib().zkmi_vk_load(ctx.h, buf.ctypes.data_as(u8p), buf.size, ctypes.byref(self.h)), "zkmi_vk_load")
+        info = np.zeros(1, np.uint64)
+        check(lib().zkmi_vk_info(self.h, _p64(info)), "zkmi_vk_info")
+        self.n_inputs = int(info[0])
+
+    def close(self):
+        if self.h:
+            lib().zkmi_vk_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def groth16_verify_many(ctx: Context, vk: VerifyingKey, proofs, inputs, rho=None):
+    """zkmi_groth16_verify_many: proofs = [(a, b, c), ...] canonical points,
+    inputs = one list of ints per proof (vk.n_inputs each).  rho: None = the
+    library draws the 128-bit weights itself (the sound use); a list of
+    non-zero ints < 2^128 fixes them (tests).  Returns ([bool per proof],
+    {"pairs", "final_exps", "invalid_points"})."""
+    nb = len(proofs)
+    if len(inputs) != nb or any(len(x) != vk.n_inputs for x in inputs):
+        raise ValueError(f"{nb} proofs need {nb} x {vk.n_inputs} public inputs")
+    if rho is not None and len(rho) != nb:
+        raise ValueError("one weight per proof")
+    a = np.ascontiguousarray([np.asarray(p[0], np.uint64) for p in proofs], np.uint64).reshape(nb, 8)
+    b = np.ascontiguousarray([np.asarray(p[1], np.uint64) for p in proofs], np.uint64).reshape(nb, 16)
+    c = np.ascontiguousarray([np.asarray(p[2], np.uint64) for p in proofs], np.uint64).reshape(nb, 8)
+    ins = np.array([[_limbs(int(v)) for v in x] for x in inputs], np.uint64).reshape(nb, vk.n_inputs, 4)
+    w = None
+    if rho is not None:
+        if any(not 0 <= int(v) < 1 << 128 for v in rho):
+            raise ValueError("weights are 128-bit values")
+        w = np.array([[int(v) & (2**64 - 1), int(v) >> 64] for v in rho], np.uint64).reshape(nb, 2)
+    valid = np.zeros(max(nb, 1), np.uint8)
+    st = VerifyStatsStruct()
+    check(lib().zkmi_groth16_verify_many(ctx.h, vk.h, nb, _p64(ins), _p64(a), _p64(b), _p64(c),
+                                         None if w is None else _p64(w), valid.ctypes.data_as(u8p), ctypes.byref(st)),
+          "zkmi_groth16_verify_many")
+    return [bool(v) for v in valid[:nb]], {"pairs": int(st.pairs), "final_exps": int(st.final_exps),
+                                           "invalid_points": int(st.invalid_points)}
 
 
 def proof_to_alt_bn128_bytes(a, b, c) -> bytes:

@@ -139,6 +139,7 @@ class Groth16Prover:
         # records the program), used when the default synthesizer is
         self._shapes: dict = {}
         self._many_z: dict = {}  # per shape: the strided z buffer of prove_many
+        self._vk = None  # resident VerifyingKey of verify_many, made on first use
 
     @classmethod
     def from_bytes(cls, pk_bytes: bytes, vk_bytes: bytes, device: int = 0, circuit=None, compressed=True,
@@ -308,6 +309,23 @@ class Groth16Prover:
         if a is None or b is None or c is None:
             a, b, c = proof_points_from_solana_bytes(proof.proof_bytes)
         return gpu.groth16_verify(self.verifying_key, public_inputs, a, b, c)
+
+    def verify_many(self, proofs, public_inputs) -> list:
+        """verify_pairing for a list of BatchProofs in one batched call
+        (zkmi_groth16_verify_many: the Miller loops on the GPU, one final
+        exponentiation for the batch, weights drawn by the library).
+        public_inputs: one list of instance values per proof.  Proofs carrying
+        only proof_bytes are decoded from them, as verify_pairing does."""
+        proofs = list(proofs)
+        if self._vk is None:
+            self._vk = gpu.VerifyingKey(self.ctx, self.verifying_key)
+        pts = []
+        for p in proofs:
+            if p.a is None or p.b is None or p.c is None:
+                pts.append(proof_points_from_solana_bytes(p.proof_bytes))
+            else:
+                pts.append((p.a, p.b, p.c))
+        return gpu.groth16_verify_many(self.ctx, self._vk, pts, list(public_inputs))[0]
 
     def verification_key_hash(self) -> bytes:
         return self.vk_hash
