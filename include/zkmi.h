@@ -494,8 +494,12 @@ int zkmi_g1_mul(const uint64_t p[8], const uint64_t k[4], uint64_t out[8]);
  * subset's three fixed pairs and one final exponentiation, at most two probes
  * a level; a subset of one is decided exactly.  A valid proof is never
  * rejected; an invalid one is accepted with probability about 2^-127 over the
- * weights.  Worst case: every proof bad costs about 2 nb probes, slower than
- * a loop of zkmi_groth16_verify (a batch is expected to be mostly valid). */
+ * weights.  Worst case without a probe budget: every proof bad costs about
+ * 2 nb probes, slower than a loop of zkmi_groth16_verify.  With a budget B
+ * (zkmi_ctx_set_verify_probes) the host runs at most B final exponentiations
+ * and the proofs still undecided then get exact verdicts from ONE pass of
+ * zkmi_groth16_verify_each's kernels, whose cost does not depend on how many
+ * proofs are bad. */
 typedef struct zkmi_vk zkmi_vk;
 /* arkworks-compressed VerifyingKey, decoded and validated once (as
  * zkmi_groth16_verify does per call); ZKMI_EPOINT for a bad key */
@@ -522,6 +526,48 @@ typedef struct {
 int zkmi_groth16_verify_many(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const uint64_t* a,
                              const uint64_t* b, const uint64_t* c, const uint64_t* rho, uint8_t* valid,
                              zkmi_verify_stats* stats);
+
+/* ------------------------------------------------- per-proof verification
+ * zkmi_groth16_verify for nb proofs under one key with EVERYTHING on the GPU
+ * (DESIGN.md section 2.8): per proof the three Miller loops of (A_i, B_i),
+ * (-X_i, gamma), (-C_i, delta), one more for (-alpha, beta) per call, and one
+ * final exponentiation per proof, a GPU lane each.  valid[i] equals
+ * zkmi_groth16_verify's verdict for proof i exactly: there are no weights and
+ * no soundness error, and the cost is the same whether the proofs are valid or
+ * not (a fixed number of launches on the context stream, no new stream).  Only
+ * the nb verdict bytes (and the validation flags) come back to the host.
+ * pairs: Miller loops run (3 nb + 1, or 0 when no proof passed point
+ * validation); final_exps: GPU final exponentiations (the proofs that passed
+ * point validation); invalid_points: as in zkmi_verify_stats. */
+typedef struct {
+  uint64_t pairs;
+  uint64_t final_exps;
+  uint64_t invalid_points;
+} zkmi_verify_each_stats;
+/* The argument rules of zkmi_groth16_verify_many: an input >= r is
+ * ZKMI_EINVAL for the whole call, a bad proof point is valid[i] = 0, nb = 0
+ * is valid and launches nothing, a key of another context is ZKMI_EINVAL.
+ * Synchronous. */
+int zkmi_groth16_verify_each(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const uint64_t* a,
+                             const uint64_t* b, const uint64_t* c, uint8_t* valid, zkmi_verify_each_stats* stats);
+/* Probe budget of zkmi_groth16_verify_many on this context.  0 (the default):
+ * unlimited, nothing changes.  B >= 1: host final exponentiations are counted,
+ * the first combined check included; once B have run, every proof not yet
+ * decided goes in one sub-batch through zkmi_groth16_verify_each's kernels
+ * (over the points already uploaded and validated), so stats.final_exps <= B
+ * and the call's cost is bounded however many proofs are bad.
+ * Recommended where bad batches can occur: 20.  Measured (DESIGN.md section
+ * 2.8) a probe costs about 6.3 ms of host time and the hand-over about 121 ms
+ * whatever nb is, so the two cost the same at about 19 probes: one bad proof
+ * among up to 1024 (at most 1 + 2 log2 nb = 21 probes, 20 measured) is still
+ * found by bisection, two or more are handed over.  The default stays 0. */
+int zkmi_ctx_set_verify_probes(zkmi_ctx* ctx, uint64_t max_probes);
+uint64_t zkmi_ctx_get_verify_probes(const zkmi_ctx* ctx);
+/* What the last zkmi_groth16_verify_many on this context handed to the GPU
+ * when its budget ran out: out = {gpu_decided (proofs), gpu_pairs (Miller
+ * loops of that sub-batch), gpu_final_exps}; all 0 when the budget was not
+ * hit. */
+int zkmi_groth16_verify_last(zkmi_ctx* ctx, uint64_t out[3]);
 
 #ifdef __cplusplus
 }

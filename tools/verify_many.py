@@ -13,6 +13,19 @@ verify_prepare / verify_miller); then ONE timed loop of zkmi_groth16_verify
 over the same nb proofs (capped at VM_HOST_CAP proofs, default 1024, and
 scaled).
 `one_bad_ms`: the batched call with one proof's input changed (bisection).
+
+    python tools/verify_many.py --each [nb ...]
+
+Per nb, on the same proofs: zkmi_groth16_verify_each on the all-valid batch
+and on the all-bad batch (every input + 1), each warmed and the median of
+VM_REPS calls with the profiler off (`*_spread_ms` = max - min of those
+calls); its four kernel times from three further calls with the profiler on;
+verify_many under the probe budget VM_BUDGET (default 1) on the all-bad batch,
+the same way; verify_many without a budget on that batch, timed ONCE (about
+2 nb probes); one bad proof without a budget (`probe_ms` = the extra time per
+extra final exponentiation, the figure the crossover is taken from); the host
+loop as above.  Against a library without verify_each (ZKMI_LIB pointing at an
+older build) only the unbudgeted and host figures are reported.
 """
 import json
 import os
@@ -29,12 +42,90 @@ HOST_CAP = int(os.environ.get("VM_HOST_CAP", "1024"))
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
 
+BUDGET = int(os.environ.get("VM_BUDGET", "1"))
+
+
+def timed(fn):
+    """fn warmed once, then REPS timed calls: (median ms, max - min ms, last result)"""
+    out = fn()
+    times = []
+    for _ in range(REPS):
+        t0 = time.perf_counter()
+        out = fn()
+        times.append(1e3 * (time.perf_counter() - t0))
+    return statistics.median(times), max(times) - min(times), out
+
+
+def each_mode(ctx, vk, vkb, base, base_in, nbs):
+    from zelana_amd import gpu
+    from zelana_amd._lib import lib
+    has_each = hasattr(lib(), "zkmi_groth16_verify_each")
+    for nb in nbs:
+        proofs = [base[i % 64] for i in range(nb)]
+        inputs = [base_in[i % 64] for i in range(nb)]
+        bad_in = [[(x[0] + 1) % R] for x in inputs]
+        row = {"nb": nb, "reps": REPS, "each": has_each}
+        if has_each:
+            ok_ms, ok_sp, (valid, st) = timed(lambda: gpu.groth16_verify_each(ctx, vk, proofs, inputs))
+            assert all(valid) and st["final_exps"] == nb
+            bad_ms, bad_sp, (valid, st) = timed(lambda: gpu.groth16_verify_each(ctx, vk, proofs, bad_in))
+            assert not any(valid) and st["final_exps"] == nb
+            row.update({"each_valid_ms": round(ok_ms, 3), "each_valid_spread_ms": round(ok_sp, 3),
+                        "each_bad_ms": round(bad_ms, 3), "each_bad_spread_ms": round(bad_sp, 3),
+                        "each_per_proof_ms": round(ok_ms / nb, 4), "pairs": st["pairs"]})
+            ctx.profile(True)
+            ctx.profile_reset()
+            for _ in range(3):
+                gpu.groth16_verify_each(ctx, vk, proofs, bad_in)
+            for name in ("verify_each_prepare", "verify_inputs", "verify_miller", "verify_final_exp"):
+                t, n = ctx.profile_get(name)
+                row[name + "_ms"] = round(t / max(n, 1), 3)
+            ctx.profile(False)
+            ctx.set_verify_probes(BUDGET)
+            bud_ms, bud_sp, (valid, st) = timed(lambda: gpu.groth16_verify_many(ctx, vk, proofs, bad_in))
+            last = gpu.groth16_verify_last(ctx)
+            ctx.set_verify_probes(0)
+            assert not any(valid) and st["final_exps"] <= BUDGET
+            row.update({"budget": BUDGET, "budgeted_all_bad_ms": round(bud_ms, 3),
+                        "budgeted_all_bad_spread_ms": round(bud_sp, 3), "budgeted_final_exps": st["final_exps"],
+                        "gpu_decided": last["gpu_decided"]})
+        t0 = time.perf_counter()
+        valid, st = gpu.groth16_verify_many(ctx, vk, proofs, bad_in)  # no budget: timed once
+        free_ms = 1e3 * (time.perf_counter() - t0)
+        assert not any(valid)
+        row.update({"unbudgeted_all_bad_ms": round(free_ms, 3), "unbudgeted_final_exps": st["final_exps"]})
+        all_ms, _, (valid, st1) = timed(lambda: gpu.groth16_verify_many(ctx, vk, proofs, inputs))
+        assert all(valid)
+        one_in = [list(x) for x in inputs]
+        one_in[nb // 2] = bad_in[nb // 2]
+        one_ms, _, (valid, stb) = timed(lambda: gpu.groth16_verify_many(ctx, vk, proofs, one_in))
+        assert valid == [i != nb // 2 for i in range(nb)]
+        extra = stb["final_exps"] - st1["final_exps"]
+        row.update({"verify_many_all_valid_ms": round(all_ms, 3), "one_bad_ms": round(one_ms, 3),
+                    "one_bad_final_exps": stb["final_exps"],
+                    "probe_ms": round((one_ms - all_ms) / extra, 3) if extra else None})
+        nh = min(nb, HOST_CAP)
+        t0 = time.perf_counter()
+        hv = [gpu.groth16_verify(vkb, bad_in[i], *proofs[i]) for i in range(nh)]
+        host_ms = 1e3 * (time.perf_counter() - t0) * nb / nh
+        assert not any(hv)
+        row.update({"host_loop_all_bad_ms": round(host_ms, 3), "host_loop_proofs_timed": nh})
+        if has_each:
+            row.update({"budgeted_vs_unbudgeted": round(free_ms / bud_ms, 2),
+                        "budgeted_vs_host_loop": round(host_ms / bud_ms, 2)})
+            if row["probe_ms"]:
+                row["crossover_probes"] = round(ok_ms / row["probe_ms"], 1)
+        print(json.dumps(row), flush=True)
+
+
 def main():
     from zelana_amd import gpu
     from zelana_amd.keygen import circuit_specific_setup
     from zelana_amd.r1cs import square_circuit
     from zelana_amd.rng import StdRng
-    nbs = [int(a) for a in sys.argv[1:]] or [1, 64, 1024]
+    args = sys.argv[1:]
+    each = "--each" in args
+    nbs = [int(a) for a in args if a != "--each"] or [1, 64, 1024]
     ctx = gpu.Context(0)
     cs, _ = square_circuit(2)
     pk, vkb = circuit_specific_setup(ctx, cs, StdRng.seed_from_u64(7))
@@ -47,6 +138,9 @@ def main():
         r, s = (int.from_bytes(rng.bytes(31), "little") for _ in range(2))
         base.append(gpu.groth16_prove(ctx, pk, cs, zz, r, s))
         base_in.append([x * x % R])
+    if each:
+        each_mode(ctx, vk, vkb, base, base_in, nbs)
+        nbs = []
     for nb in nbs:
         proofs = [base[i % 64] for i in range(nb)]
         inputs = [base_in[i % 64] for i in range(nb)]

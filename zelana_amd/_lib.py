@@ -50,7 +50,7 @@ ROW_NONE = 2**64 - 1  # ZKMI_ROW_NONE
 
 
 class VerifyStatsStruct(ctypes.Structure):
-    """zkmi_verify_stats"""
+    """zkmi_verify_stats / zkmi_verify_each_stats (the same three counters)"""
     _fields_ = [("pairs", ctypes.c_uint64), ("final_exps", ctypes.c_uint64), ("invalid_points", ctypes.c_uint64)]
 
 
@@ -151,6 +151,11 @@ SIGNATURES = [
     ("zkmi_vk_info", ctypes.c_int, [vp, u64p]),
     ("zkmi_groth16_verify_many", ctypes.c_int, [vp, vp, sz, u64p, u64p, u64p, u64p, u64p, u8p,
                                                 ctypes.POINTER(VerifyStatsStruct)]),
+    ("zkmi_groth16_verify_each", ctypes.c_int, [vp, vp, sz, u64p, u64p, u64p, u64p, u8p,
+                                                ctypes.POINTER(VerifyStatsStruct)]),
+    ("zkmi_ctx_set_verify_probes", ctypes.c_int, [vp, ctypes.c_uint64]),
+    ("zkmi_ctx_get_verify_probes", ctypes.c_uint64, [vp]),
+    ("zkmi_groth16_verify_last", ctypes.c_int, [vp, u64p]),
     ("zkmi_proof_to_solana_bytes", ctypes.c_int, [u64p, u64p, u64p, u8p]),
     ("zkmi_proof_serialize_compressed", ctypes.c_int, [u64p, u64p, u64p, u8p]),
 ]

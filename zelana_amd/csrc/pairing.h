@@ -1,6 +1,8 @@
-// pairing.h — Fq12 arithmetic and the single-pair Tate Miller loop of the
-// batched verifier (pairing.hip k_miller), host+device like ff.h / ec.h so the
-// same code runs in a stand-alone host check (tests/host/pairing_dev_check.cpp).
+// pairing.h — Fq12 arithmetic, the single-pair Tate Miller loop of the batched
+// verifier (pairing.hip k_miller) and the final exponentiation of verify_each
+// (k_final_exp), host+device like ff.h / ec.h so the same code runs in
+// stand-alone host checks (tests/host/pairing_dev_check.cpp,
+// final_exp_dev_check.cpp).
 //
 // Fq12 = Fq[w] / (w^12 - 18 w^6 + 82): 12 Fq coefficients of w^0 .. w^11, the
 // representation of verify.cpp, so values compare coefficient by coefficient.
@@ -325,6 +327,53 @@ ZK_HD int miller_loop(A& f0, A& f1, const Fe& px, const Fe& py, const Fe2& qx, c
     }
   }
   return cur;
+}
+
+// ------------------------------------------------------------ final exponentiation
+// What verify.cpp's final_exp_is_one decides, for verify_each's k_final_exp:
+// with h = (f^(q^2) f)^((q^4 - q^2 + 1) / r), true iff h != 0 and h lies in
+// Fq6 = span{w^even}.  q = 1 mod 6, so w^(q^2) = zeta w with zeta in Fq and
+// Frobenius^2 multiplies coefficient i by zeta^i.
+struct FinalExpConst {
+  Fe zeta[12];        // zeta^i, Montgomery (verify.cpp's frob2_table)
+  uint64_t hard[12];  // (q^4 - q^2 + 1) / r, little-endian (verify.cpp's HARD)
+};
+constexpr int HARD_BITS = 761;  // bit 760 is the exponent's top bit
+template <class O, class A>
+ZK_HD void f12_frob2(O& out, const A& a, const Fe* zeta) {
+#pragma unroll 1
+  for (int i = 0; i < 12; i++) out.set(i, mul<FqP>(a.get(i), zeta[i]));
+}
+// f holds the Miller value and is overwritten; t0 and t1 are two more
+// elements' storage.  Plain left-to-right square-and-multiply over the 761
+// bits of the exponent (weight 389: 760 squares, 388 products): t1 keeps the
+// base, f and t0 ping-pong.  Every lane of a wave runs the same bits.  The
+// verdict compares fully reduced values (is_zero reduces [0, 2p) to [0, p)).
+template <class A>
+ZK_HD bool final_exp_is_one(A& f, A& t0, A& t1, const Fe* zeta, const uint64_t* hard) {
+  const F12Const K = f12_const();
+  f12_frob2(t0, f, zeta);
+  f12_mul(t1, t0, f, K);
+#pragma unroll 1
+  for (int i = 0; i < 12; i++) f.set(i, t1.get(i));
+  int cur = 0;  // the running power lives in f (0) or t0 (1)
+#pragma unroll 1
+  for (int bit = HARD_BITS - 2; bit >= 0; bit--) {
+    if (cur == 0) f12_sqr(t0, f, K); else f12_sqr(f, t0, K);
+    cur ^= 1;
+    if ((hard[bit >> 6] >> (bit & 63)) & 1) {
+      if (cur == 0) f12_mul(t0, f, t1, K); else f12_mul(f, t0, t1, K);
+      cur ^= 1;
+    }
+  }
+  bool nonzero = false, odd_zero = true;
+#pragma unroll 1
+  for (int i = 0; i < 12; i++) {
+    const bool z = is_zero<FqP>(cur == 0 ? f.get(i) : t0.get(i));
+    nonzero |= !z;
+    if (i & 1) odd_zero &= z;
+  }
+  return nonzero && odd_zero;
 }
 
 }  // namespace zk

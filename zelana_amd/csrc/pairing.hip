@@ -5,9 +5,18 @@
 //   k_miller          one lane per pair: the Tate Miller loop of pairing.h
 // and the host half in verify.cpp (verify_many_combine): one final
 // exponentiation for the batch, bisection when the combined check fails.
+// And exact per-proof verdicts (zkmi_groth16_verify_each):
+//   k_verify_each_prepare  the same validation, the pairs (A_i, B_i), (-C_i, delta)
+//   k_verify_input_terms / k_verify_inputs  -X_i = -(IC[0] + sum_j x_ij IC[j+1])
+//   k_miller               over 3 nb + 1 pairs
+//   k_final_exp            one lane per proof: the final exponentiation and
+//                          the verdict, the only thing downloaded
+// which verify_many also uses for the proofs its bisection leaves undecided
+// once a probe budget (zkmi_ctx_set_verify_probes) is spent.
 #include <string.h>
 #include <sys/random.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "dev_io.h"
@@ -82,11 +91,47 @@ __device__ __forceinline__ void v_g1_mul128(const Aff<FqOps>& p, uint4 k, uint32
   st_fe(out + 8, from_mont<FqP>(mul<FqP>(acc.y, mul<FqP>(inv, acc.zz))));
 }
 
-// One lane per proof.  bad[i] = 1 when zkmi_groth16_verify would call proof i
-// invalid for its points alone: a coordinate >= q, A or C off the curve, B
-// off the twist or outside the order-r subgroup ([r] B, the loop of
-// k_decode_g2).  The all-zero encoding is the point at infinity (valid).
-// Otherwise pairs[i] = (rho_i A_i, B_i) and rc[i] = rho_i C_i.
+// Point validation of one proof (wa, wb, wc: its canonical A, B, C), shared by
+// k_verify_prepare and k_verify_each_prepare.  False when zkmi_groth16_verify
+// would call the proof invalid for its points alone: a coordinate >= q, A or C
+// off the curve, B off the twist or outside the order-r subgroup ([r] B, the
+// loop of k_decode_g2).  The all-zero encoding is the point at infinity
+// (valid).  A and C come back in Montgomery form.
+struct VPoints {
+  bool a_inf, b_inf, c_inf;
+  Aff<FqOps> A, C;
+};
+__device__ __forceinline__ bool v_validate(const uint32_t* wa, const uint32_t* wb, const uint32_t* wc, VPoints& p) {
+  bool lt = true;
+#pragma unroll
+  for (int t = 0; t < 2; t++) lt &= v_lt_q(wa + 8 * t) && v_lt_q(wc + 8 * t);
+#pragma unroll
+  for (int t = 0; t < 4; t++) lt &= v_lt_q(wb + 8 * t);
+  if (!lt) return false;
+  p.a_inf = v_all_zero(wa, 16);
+  p.b_inf = v_all_zero(wb, 32);
+  p.c_inf = v_all_zero(wc, 16);
+  p.A = {v_fe(wa), v_fe(wa + 8)};
+  p.C = {v_fe(wc), v_fe(wc + 8)};
+  if (!p.a_inf && !v_g1_on_curve(p.A.x, p.A.y)) return false;
+  if (!p.c_inf && !v_g1_on_curve(p.C.x, p.C.y)) return false;
+  if (!p.b_inf) {
+    const Aff<Fq2Ops> B = {{v_fe(wb), v_fe(wb + 8)}, {v_fe(wb + 16), v_fe(wb + 24)}};
+    const Fe2 tb = {to_mont<FqP>(ldc_fe(VG2B_C0)), to_mont<FqP>(ldc_fe(VG2B_C1))};
+    const Fe2 lhs = f2_sqr(B.y), rhs = f2_add(f2_mul(f2_sqr(B.x), B.x), tb);
+    if (!eq<FqP>(lhs.c0, rhs.c0) || !eq<FqP>(lhs.c1, rhs.c1)) return false;
+    Xyzz<Fq2Ops> acc = xyzz_inf<Fq2Ops>();
+    for (int bit = 253; bit >= 0; bit--) {
+      acc = xyzz_dbl(acc);
+      if ((VR_MOD64[bit >> 6] >> (bit & 63)) & 1) acc = xyzz_madd(acc, B);
+    }
+    if (!xyzz_is_inf(acc)) return false;
+  }
+  return true;
+}
+
+// One lane per proof.  bad[i] = 1 when the proof fails point validation
+// (v_validate).  Otherwise pairs[i] = (rho_i A_i, B_i) and rc[i] = rho_i C_i.
 __global__ void __launch_bounds__(VB) k_verify_prepare(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
                                                        const uint32_t* __restrict__ c,
                                                        const uint32_t* __restrict__ rho, size_t nb,
@@ -103,28 +148,10 @@ __global__ void __launch_bounds__(VB) k_verify_prepare(const uint32_t* __restric
   for (int t = 0; t < 16; t++) wc[t] = c[i * 16 + t];
   const uint4 k = reinterpret_cast<const uint4*>(rho)[i];
   bad[i] = 1;
-  bool lt = true;
-#pragma unroll
-  for (int t = 0; t < 2; t++) lt &= v_lt_q(wa + 8 * t) && v_lt_q(wc + 8 * t);
-#pragma unroll
-  for (int t = 0; t < 4; t++) lt &= v_lt_q(wb + 8 * t);
-  if (!lt) return;
-  const bool a_inf = v_all_zero(wa, 16), b_inf = v_all_zero(wb, 32), c_inf = v_all_zero(wc, 16);
-  const Aff<FqOps> A = {v_fe(wa), v_fe(wa + 8)}, C = {v_fe(wc), v_fe(wc + 8)};
-  if (!a_inf && !v_g1_on_curve(A.x, A.y)) return;
-  if (!c_inf && !v_g1_on_curve(C.x, C.y)) return;
-  if (!b_inf) {
-    const Aff<Fq2Ops> B = {{v_fe(wb), v_fe(wb + 8)}, {v_fe(wb + 16), v_fe(wb + 24)}};
-    const Fe2 tb = {to_mont<FqP>(ldc_fe(VG2B_C0)), to_mont<FqP>(ldc_fe(VG2B_C1))};
-    const Fe2 lhs = f2_sqr(B.y), rhs = f2_add(f2_mul(f2_sqr(B.x), B.x), tb);
-    if (!eq<FqP>(lhs.c0, rhs.c0) || !eq<FqP>(lhs.c1, rhs.c1)) return;
-    Xyzz<Fq2Ops> acc = xyzz_inf<Fq2Ops>();
-    for (int bit = 253; bit >= 0; bit--) {
-      acc = xyzz_dbl(acc);
-      if ((VR_MOD64[bit >> 6] >> (bit & 63)) & 1) acc = xyzz_madd(acc, B);
-    }
-    if (!xyzz_is_inf(acc)) return;
-  }
+  VPoints vp;
+  if (!v_validate(wa, wb, wc, vp)) return;
+  const bool a_inf = vp.a_inf, c_inf = vp.c_inf;
+  const Aff<FqOps> A = vp.A, C = vp.C;
   bad[i] = 0;
   uint32_t* o = pairs + i * PAIR_WORDS;
 #pragma unroll
@@ -187,6 +214,292 @@ __global__ void __launch_bounds__(VB) k_miller(const uint32_t* __restrict__ pair
   const int cur = miller_loop(f[0], f[1], v_fe(w), v_fe(w + 8), qx, qy);
   const F12Lds r = {&lds[cur][threadIdx.x]};
   for (int t = 0; t < 12; t++) st_fe(o + 8 * t, from_mont<FqP>(r.get(t)));
+}
+
+// ------------------------------------------------------------ verify_each
+// Exact per-proof verdicts (zkmi_groth16_verify_each): for n
+// proofs the pair list is
+//   [0, n)      (A_i, B_i)          k_verify_each_prepare
+//   [n, 2n)     (-X_i, gamma)       k_verify_inputs
+//   [2n, 3n)    (-C_i, delta)       k_verify_each_prepare
+//   3n          (-alpha, beta)      the host, once a call
+// so k_miller's flag test (i < nbad) covers the first n lanes; the G1 side of
+// a flagged proof's other two pairs is written as infinity (Miller value 1).
+constexpr int XYZZ_WORDS = 4 * NL;                   // one G1 term of X_i, Montgomery limbs
+constexpr size_t EACH_TERM_BYTES = (size_t)96 << 20;  // term workspace of a chunk of proofs
+
+// One lane per proof: lane t works on proof sel[t] of the uploaded arrays
+// (sel = NULL: proof t).  With sel the proofs were validated by an earlier
+// k_verify_prepare and are taken as they are; without, bad[t] is set as
+// k_verify_prepare sets it.  No weights.
+__global__ void __launch_bounds__(VB) k_verify_each_prepare(const uint32_t* __restrict__ a,
+                                                            const uint32_t* __restrict__ b,
+                                                            const uint32_t* __restrict__ c,
+                                                            const uint32_t* __restrict__ sel, size_t n,
+                                                            const uint32_t* __restrict__ delta,
+                                                            uint32_t* __restrict__ pairs, uint32_t* __restrict__ bad) {
+  const size_t t = blockIdx.x * (size_t)VB + threadIdx.x;
+  if (t >= n) return;
+  const size_t i = sel ? sel[t] : t;
+  uint32_t wa[16], wb[32], wc[16];
+#pragma unroll
+  for (int k = 0; k < 16; k++) wa[k] = a[i * 16 + k];
+#pragma unroll
+  for (int k = 0; k < 32; k++) wb[k] = b[i * 32 + k];
+#pragma unroll
+  for (int k = 0; k < 16; k++) wc[k] = c[i * 16 + k];
+  uint32_t* oc = pairs + (2 * n + t) * PAIR_WORDS;
+#pragma unroll
+  for (int k = 0; k < 32; k++) oc[16 + k] = delta[k];
+  bool ok = true;
+  if (!sel) {
+    VPoints vp;
+    ok = v_validate(wa, wb, wc, vp);
+  }
+  bad[t] = ok ? 0 : 1;
+  if (!ok || v_all_zero(wc, 16)) {
+    for (int k = 0; k < 16; k++) oc[k] = 0;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) oc[k] = wc[k];
+    st_fe(oc + 8, from_mont<FqP>(neg<FqP>(v_fe(wc + 8))));  // -C
+  }
+  if (!ok) return;
+  uint32_t* o = pairs + t * PAIR_WORDS;
+#pragma unroll
+  for (int k = 0; k < 16; k++) o[k] = wa[k];
+#pragma unroll
+  for (int k = 0; k < 32; k++) o[16 + k] = wb[k];
+}
+
+// One lane per (proof, input) of a chunk of np proofs starting at proof p0:
+// terms[g] = x_ij IC[j+1] by 254-bit double-and-add (x < r), XYZZ in Montgomery
+// limbs; infinity (all zero) for x = 0 or an IC point at infinity.  ic: the
+// key's n_in + 1 points, canonical affine; inputs: 8 u32 per value.
+__global__ void __launch_bounds__(VB) k_verify_input_terms(const uint32_t* __restrict__ ic,
+                                                           const uint32_t* __restrict__ inputs,
+                                                           const uint32_t* __restrict__ bad, size_t p0, size_t np,
+                                                           size_t n_in, uint32_t* __restrict__ terms) {
+  const size_t g = blockIdx.x * (size_t)VB + threadIdx.x;
+  if (g >= np * n_in) return;
+  const size_t i = p0 + g / n_in, j = g % n_in;
+  if (bad[i]) return;  // k_verify_inputs does not read a flagged proof's terms
+  uint32_t w[16];
+#pragma unroll
+  for (int k = 0; k < 16; k++) w[k] = ic[(j + 1) * 16 + k];
+  Xyzz<FqOps> acc = xyzz_inf<FqOps>();
+  if (!v_all_zero(w, 16)) {
+    const Aff<FqOps> P = {v_fe(w), v_fe(w + 8)};
+    const uint32_t* x = inputs + (i * n_in + j) * 8;
+    for (int word = 7; word >= 0; word--) {
+      const uint32_t kw = x[word];
+      for (int bit = 31; bit >= 0; bit--) {
+        acc = xyzz_dbl(acc);
+        if ((kw >> bit) & 1) acc = xyzz_madd(acc, P);
+      }
+    }
+  }
+  uint32_t* o = terms + g * XYZZ_WORDS;
+#pragma unroll
+  for (int l = 0; l < NL; l++) {
+    o[l] = acc.x.v[l];
+    o[NL + l] = acc.y.v[l];
+    o[2 * NL + l] = acc.zz.v[l];
+    o[3 * NL + l] = acc.zzz.v[l];
+  }
+}
+
+// One lane per proof of the chunk: pairs[n + i] = (-X_i, gamma) with
+// X_i = IC[0] + sum_j terms[i][j], canonical affine by one Fermat inversion
+// (as v_g1_mul128); the G1 side is infinity for a flagged proof or X_i = O.
+__global__ void __launch_bounds__(VB) k_verify_inputs(const uint32_t* __restrict__ ic,
+                                                      const uint32_t* __restrict__ terms,
+                                                      const uint32_t* __restrict__ bad, size_t p0, size_t np, size_t n,
+                                                      size_t n_in, const uint32_t* __restrict__ gamma,
+                                                      uint32_t* __restrict__ pairs) {
+  const size_t t = blockIdx.x * (size_t)VB + threadIdx.x;
+  if (t >= np) return;
+  const size_t i = p0 + t;
+  uint32_t* o = pairs + (n + i) * PAIR_WORDS;
+#pragma unroll
+  for (int k = 0; k < 32; k++) o[16 + k] = gamma[k];
+  Xyzz<FqOps> acc = xyzz_inf<FqOps>();
+  if (!bad[i]) {
+    uint32_t w[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) w[k] = ic[k];
+    if (!v_all_zero(w, 16)) acc = xyzz_from_aff<FqOps>({v_fe(w), v_fe(w + 8)});
+#pragma unroll 1
+    for (size_t j = 0; j < n_in; j++) {
+      const uint32_t* s = terms + (t * n_in + j) * XYZZ_WORDS;
+      Xyzz<FqOps> q;
+#pragma unroll
+      for (int l = 0; l < NL; l++) {
+        q.x.v[l] = s[l];
+        q.y.v[l] = s[NL + l];
+        q.zz.v[l] = s[2 * NL + l];
+        q.zzz.v[l] = s[3 * NL + l];
+      }
+      acc = xyzz_add(acc, q);
+    }
+  }
+  if (xyzz_is_inf(acc)) {
+    for (int k = 0; k < 16; k++) o[k] = 0;
+    return;
+  }
+  const uint64_t qm2[4] = {0x3c208c16d87cfd45ull, 0x97816a916871ca8dull, 0xb85045b68181585dull,
+                           0x30644e72e131a029ull};
+  const Fe inv = pow<FqP>(mul<FqP>(acc.zz, acc.zzz), qm2);
+  st_fe(o, from_mont<FqP>(mul<FqP>(acc.x, mul<FqP>(inv, acc.zzz))));
+  st_fe(o + 8, from_mont<FqP>(neg<FqP>(mul<FqP>(acc.y, mul<FqP>(inv, acc.zz)))));
+}
+
+// One lane per proof: valid[i] = whether the product of the proof's three
+// Miller values f[i], f[n + i], f[2n + i] and the shared f[3n] passes the
+// final exponentiation (pairing.h final_exp_is_one); 0 with no work for a
+// flagged proof.  LDS: three elements per lane (the chain's base and the two
+// it ping-pongs between), 3 x 12 x 9 x 64 x 4 B = 82,944 B a block, so one
+// block a CU; no barriers (every column is private to its lane).  The
+// exponent's bits are the same for every lane: the wave diverges only on the
+// flags.
+__global__ void __launch_bounds__(VB) k_final_exp(const uint32_t* __restrict__ f, const uint32_t* __restrict__ bad,
+                                                  size_t n, const FinalExpConst* __restrict__ fc,
+                                                  uint8_t* __restrict__ valid) {
+  __shared__ uint32_t lds[3][12 * NL * VB];
+  const size_t i = blockIdx.x * (size_t)VB + threadIdx.x;
+  if (i >= n) return;
+  if (bad[i]) {
+    valid[i] = 0;
+    return;
+  }
+  F12Lds e0 = {&lds[0][threadIdx.x]}, e1 = {&lds[1][threadIdx.x]}, e2 = {&lds[2][threadIdx.x]};
+  const F12Const K = f12_const();
+  const uint32_t* src = f + i * F12_WORDS;
+#pragma unroll 1
+  for (int t = 0; t < 12; t++) {
+    e0.set(t, to_mont<FqP>(ld_fe(src + 8 * t)));
+    e1.set(t, to_mont<FqP>(ld_fe(src + n * F12_WORDS + 8 * t)));
+  }
+  f12_mul(e2, e0, e1, K);
+#pragma unroll 1
+  for (int t = 0; t < 12; t++) e0.set(t, to_mont<FqP>(ld_fe(src + 2 * n * F12_WORDS + 8 * t)));
+  f12_mul(e1, e2, e0, K);
+#pragma unroll 1
+  for (int t = 0; t < 12; t++) e0.set(t, to_mont<FqP>(ld_fe(f + 3 * n * F12_WORDS + 8 * t)));
+  f12_mul(e2, e1, e0, K);
+  valid[i] = final_exp_is_one(e2, e0, e1, fc->zeta, fc->hard) ? 1 : 0;
+}
+
+static unsigned vblocks(size_t n) { return (unsigned)((n + VB - 1) / VB); }
+
+// verify.cpp's Frobenius^2 constants and exponent, in the device's form
+static const FinalExpConst& final_exp_const() {
+  static const FinalExpConst fc = [] {
+    FinalExpConst c;
+    uint64_t zeta[48];
+    zkv::final_exp_constants(zeta, c.hard);
+    for (int i = 0; i < 12; i++) {
+      uint32_t w[8];
+      memcpy(w, zeta + 4 * i, 32);
+      c.zeta[i] = to_mont<FqP>(unpack(w));
+    }
+    return c;
+  }();
+  return fc;
+}
+
+// The kernels of verify_each over n lanes: lane t is proof d_sel[t] of the
+// uploaded d_a / d_b / d_c (d_sel = NULL: proof t, validated here); inputs are
+// in lane order (n x n_inputs x 4 u64, each < r).  valid[n]; *invalid = lanes
+// that failed point validation; *pairs / *fexps = Miller loops and final
+// exponentiations run (0 when no lane passed validation).  Everything on the
+// context stream; returns after the verdicts are on the host.
+static int verify_each_run(zkmi_ctx* ctx, const zkmi_vk* vk, size_t n, const uint32_t* d_a, const uint32_t* d_b,
+                           const uint32_t* d_c, const uint32_t* d_sel, const uint64_t* inputs, uint8_t* valid,
+                           uint64_t* pairs, uint64_t* fexps, uint64_t* invalid) {
+  const size_t n_in = vk->vk.ic.size() - 1, np = 3 * n + 1;
+  const size_t chunk = std::min(n, std::max<size_t>(1, EACH_TERM_BYTES / (std::max<size_t>(1, n_in) * XYZZ_WORDS * 4)));
+  uint32_t *d_pairs, *d_bad, *d_f, *d_key, *d_x, *d_terms;
+  FinalExpConst* d_fc;
+  uint8_t* d_valid;
+  ZK_TRY(ctx->ws.get("ve_pairs", np * PAIR_WORDS * 4, (void**)&d_pairs));
+  ZK_TRY(ctx->ws.get("ve_bad", n * 4, (void**)&d_bad));
+  ZK_TRY(ctx->ws.get("ve_f", np * F12_WORDS * 4, (void**)&d_f));
+  ZK_TRY(ctx->ws.get("ve_key", (64 + (n_in + 1) * 16) * 4, (void**)&d_key));
+  ZK_TRY(ctx->ws.get("ve_x", std::max<size_t>(1, n * n_in) * 32, (void**)&d_x));
+  ZK_TRY(ctx->ws.get("ve_terms", std::max<size_t>(1, chunk * n_in) * XYZZ_WORDS * 4, (void**)&d_terms));
+  ZK_TRY(ctx->ws.get("ve_fc", sizeof(FinalExpConst), (void**)&d_fc));
+  ZK_TRY(ctx->ws.get("ve_valid", n, (void**)&d_valid));
+  // the key: delta | gamma | IC, and the call's one shared pair (-alpha, beta)
+  std::vector<uint64_t> key(32 + (n_in + 1) * 8);
+  memcpy(key.data(), vk->g2[2], 128);
+  memcpy(key.data() + 16, vk->g2[1], 128);
+  for (size_t j = 0; j <= n_in; j++) zkv::g1_to_canon(key.data() + 32 + 8 * j, vk->vk.ic[j]);
+  uint64_t shared[24];
+  zkv::g1_to_canon(shared, zkv::g1_neg(vk->vk.alpha));
+  memcpy(shared + 8, vk->g2[0], 128);
+  const uint32_t *d_delta = d_key, *d_gamma = d_key + 32, *d_ic = d_key + 64;
+  ZK_HIP(hipMemcpyAsync(d_key, key.data(), key.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(d_pairs + 3 * n * PAIR_WORDS, shared, sizeof(shared), hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(d_fc, &final_exp_const(), sizeof(FinalExpConst), hipMemcpyHostToDevice, ctx->stream));
+  if (n_in) ZK_HIP(hipMemcpyAsync(d_x, inputs, n * n_in * 32, hipMemcpyHostToDevice, ctx->stream));
+  {
+    ScopedKernelTimer tm(ctx, "verify_each_prepare");
+    k_verify_each_prepare<<<vblocks(n), VB, 0, ctx->stream>>>(d_a, d_b, d_c, d_sel, n, d_delta, d_pairs, d_bad);
+  }
+  ZK_HIP(hipGetLastError());
+  *pairs = *fexps = *invalid = 0;
+  if (!d_sel) {  // how many lanes are left decides whether anything more runs
+    std::vector<uint32_t> bad32(n);
+    ZK_HIP(hipMemcpyAsync(bad32.data(), d_bad, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; i++) *invalid += bad32[i] != 0;
+    if (*invalid == n) {
+      memset(valid, 0, n);
+      return timer_flush(ctx);
+    }
+  }
+  {
+    ScopedKernelTimer tm(ctx, "verify_inputs");
+    for (size_t p0 = 0; p0 < n; p0 += chunk) {
+      const size_t cp = std::min(chunk, n - p0);
+      if (n_in)
+        k_verify_input_terms<<<vblocks(cp * n_in), VB, 0, ctx->stream>>>(d_ic, d_x, d_bad, p0, cp, n_in, d_terms);
+      k_verify_inputs<<<vblocks(cp), VB, 0, ctx->stream>>>(d_ic, d_terms, d_bad, p0, cp, n, n_in, d_gamma, d_pairs);
+    }
+  }
+  ZK_HIP(hipGetLastError());
+  {
+    ScopedKernelTimer tm(ctx, "verify_miller");
+    k_miller<<<vblocks(np), VB, 0, ctx->stream>>>(d_pairs, d_bad, n, np, d_f);
+  }
+  ZK_HIP(hipGetLastError());
+  {
+    ScopedKernelTimer tm(ctx, "verify_final_exp");
+    k_final_exp<<<vblocks(n), VB, 0, ctx->stream>>>(d_f, d_bad, n, d_fc, d_valid);
+  }
+  ZK_HIP(hipGetLastError());
+  ZK_HIP(hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  *pairs = np;
+  *fexps = n - *invalid;
+  return timer_flush(ctx);
+}
+
+static int verify_each(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const uint64_t* a,
+                       const uint64_t* b, const uint64_t* c, uint8_t* valid, zkmi_verify_each_stats* stats) {
+  const size_t n_in = vk->vk.ic.size() - 1;
+  ZK_TRY(zkv::verify_many_check_scalars(nb, n_in, inputs, nullptr));
+  uint32_t* d_in;
+  ZK_TRY(ctx->ws.get("vm_in", nb * 68 * 4, (void**)&d_in));
+  uint32_t *d_a = d_in, *d_b = d_a + nb * 16, *d_c = d_b + nb * 32;
+  ZK_HIP(hipMemcpyAsync(d_a, a, nb * 64, hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(d_b, b, nb * 128, hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(d_c, c, nb * 64, hipMemcpyHostToDevice, ctx->stream));
+  uint64_t pairs, fexps, invalid;
+  ZK_TRY(verify_each_run(ctx, vk, nb, d_a, d_b, d_c, nullptr, inputs, valid, &pairs, &fexps, &invalid));
+  if (stats) *stats = {pairs, fexps, invalid};
+  return 0;
 }
 
 static int draw_weights(uint64_t* w, size_t nb) {
@@ -276,7 +589,31 @@ static int verify_many(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64
   for (size_t i = 0; i < np; i++) f[i] = zkv::f12_from_canon(f64.data() + 48 * i);
   const zkv::F12 fixed_all = zkv::f12_mul(zkv::f12_mul(f[nb], f[nb + 1]), f[nb + 2]);
   if (stats) stats->pairs = np;
-  return zkv::verify_many_combine(in, &fixed_all, valid, stats);
+  if (!ctx->verify_probes) return zkv::verify_many_combine(in, &fixed_all, valid, stats);
+  // a probe budget: what bisection has not decided when it is spent goes, as
+  // ONE sub-batch over the points already uploaded and validated, through the
+  // kernels of verify_each
+  std::vector<size_t> und;
+  ZK_TRY(zkv::verify_many_combine_budget(in, &fixed_all, ctx->verify_probes, valid, stats, &und));
+  if (und.empty()) return 0;
+  const size_t m = und.size();
+  std::vector<uint32_t> sel(m);
+  std::vector<uint64_t> sub_in(m * n_inputs * 4);
+  for (size_t t = 0; t < m; t++) {
+    sel[t] = (uint32_t)und[t];
+    if (n_inputs) memcpy(sub_in.data() + t * n_inputs * 4, inputs + und[t] * n_inputs * 4, n_inputs * 32);
+  }
+  uint32_t* d_sel;
+  ZK_TRY(ctx->ws.get("ve_sel", m * 4, (void**)&d_sel));
+  ZK_HIP(hipMemcpyAsync(d_sel, sel.data(), m * 4, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<uint8_t> sub_valid(m);
+  uint64_t gp, ge, gi;
+  ZK_TRY(verify_each_run(ctx, vk, m, d_a, d_b, d_c, d_sel, sub_in.data(), sub_valid.data(), &gp, &ge, &gi));
+  for (size_t t = 0; t < m; t++) valid[und[t]] = sub_valid[t];
+  ctx->verify_last[0] = m;
+  ctx->verify_last[1] = gp;
+  ctx->verify_last[2] = ge;
+  return 0;
 }
 
 }  // namespace zk
@@ -322,6 +659,7 @@ int zkmi_groth16_verify_many(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const 
     return ZKMI_EINVAL;
   }
   if (stats) memset(stats, 0, sizeof(*stats));
+  ctx->verify_last[0] = ctx->verify_last[1] = ctx->verify_last[2] = 0;
   if (nb == 0) return 0;
   if (!a || !b || !c || !valid || (vk->vk.ic.size() > 1 && !inputs)) {
     set_error("zkmi_groth16_verify_many: null argument");
@@ -329,6 +667,40 @@ int zkmi_groth16_verify_many(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const 
   }
   ZK_DEVICE_GUARD(ctx);
   return verify_many(ctx, vk, nb, inputs, a, b, c, rho, valid, stats);
+}
+
+int zkmi_groth16_verify_each(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const uint64_t* a,
+                             const uint64_t* b, const uint64_t* c, uint8_t* valid, zkmi_verify_each_stats* stats) {
+  if (!ctx || !vk || vk->ctx != ctx) {
+    set_error("zkmi_groth16_verify_each: null context or key, or a key of another context");
+    return ZKMI_EINVAL;
+  }
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (nb == 0) return 0;
+  if (!a || !b || !c || !valid || (vk->vk.ic.size() > 1 && !inputs)) {
+    set_error("zkmi_groth16_verify_each: null argument");
+    return ZKMI_EINVAL;
+  }
+  ZK_DEVICE_GUARD(ctx);
+  return verify_each(ctx, vk, nb, inputs, a, b, c, valid, stats);
+}
+
+int zkmi_ctx_set_verify_probes(zkmi_ctx* ctx, uint64_t max_probes) {
+  if (!ctx) {
+    set_error("zkmi_ctx_set_verify_probes: null context");
+    return ZKMI_EINVAL;
+  }
+  ctx->verify_probes = max_probes;
+  return 0;
+}
+uint64_t zkmi_ctx_get_verify_probes(const zkmi_ctx* ctx) { return ctx ? ctx->verify_probes : 0; }
+int zkmi_groth16_verify_last(zkmi_ctx* ctx, uint64_t out[3]) {
+  if (!ctx || !out) {
+    set_error("zkmi_groth16_verify_last: null argument");
+    return ZKMI_EINVAL;
+  }
+  memcpy(out, ctx->verify_last, sizeof(ctx->verify_last));
+  return 0;
 }
 
 }  // extern "C"

@@ -464,6 +464,13 @@ bool final_exp_is_one(const F12& f) {
     if (!fzero(h.c[i])) return false;
   return true;
 }
+// the constants of the device final exponentiation (pairing.h FinalExpConst),
+// from the tables above: w^(q^2) = zeta w, so frob2_table()[i] is zeta^i w^i
+void final_exp_constants(uint64_t zeta[48], uint64_t hard[12]) {
+  const F12* t = frob2_table();
+  for (int i = 0; i < 12; i++) to_canon(zeta + 4 * i, t[i].c[i]);
+  memcpy(hard, HARD, sizeof(HARD));
+}
 // prod_k e(P_k, Q_k) == 1
 bool pairing_product_is_one(const std::vector<G1>& ps, const std::vector<G2>& qs) {
   return final_exp_is_one(miller_value(ps, qs));
@@ -622,13 +629,13 @@ void wide_mod_r(uint64_t out[4], const Wide& a) {
 
 int verify_many_check_scalars(size_t nb, size_t n_inputs, const uint64_t* inputs, const uint64_t* rho) {
   for (size_t i = 0; i < nb; i++) {
-    if ((rho[2 * i] | rho[2 * i + 1]) == 0) {
+    if (rho && (rho[2 * i] | rho[2 * i + 1]) == 0) {
       zk::set_error("zkmi_groth16_verify_many: weight %zu is zero", i);
       return ZKMI_EINVAL;
     }
     for (size_t j = 0; j < n_inputs; j++)
       if (geq(inputs + 4 * (i * n_inputs + j), RP)) {
-        zk::set_error("zkmi_groth16_verify_many: public input %zu of proof %zu not reduced mod r", j, i);
+        zk::set_error("batched verification: public input %zu of proof %zu not reduced mod r", j, i);
         return ZKMI_EINVAL;
       }
   }
@@ -658,7 +665,11 @@ namespace {
 struct Bisect {
   const VerifyManyIn& in;
   uint8_t* valid;
+  uint64_t max_probes;               // 0 = unlimited
+  std::vector<size_t>* undecided;    // subsets left when the budget is spent
   uint64_t probes = 0;
+  enum { PASS, FAIL, UNKNOWN };
+  bool spent() const { return max_probes && probes >= max_probes; }
   // does the subset's combined check hold?  (subset product of the per-proof
   // Miller values, the subset's three fixed pairs on the host, one final
   // exponentiation)
@@ -670,34 +681,48 @@ struct Bisect {
     probes++;
     return final_exp_is_one(f);
   }
-  // known_fail: the subset is already known not to pass.  Returns whether it
-  // passed.  A subset of one is exact: rho_i is invertible mod r.
-  bool solve(const size_t* idx, size_t n, bool known_fail) {
-    if (n == 0) return true;
-    if (!known_fail && probe(idx, n)) {
-      for (size_t t = 0; t < n; t++) valid[idx[t]] = 1;
-      return true;
+  // known_fail: the subset is already known not to pass.  A subset of one is
+  // exact: rho_i is invertible mod r.  A subset that needs a probe after the
+  // budget is spent is handed back whole (UNKNOWN), and nothing is inferred
+  // from it for its sibling.
+  int solve(const size_t* idx, size_t n, bool known_fail) {
+    if (n == 0) return PASS;
+    if (!known_fail) {
+      if (spent()) {
+        undecided->insert(undecided->end(), idx, idx + n);
+        return UNKNOWN;
+      }
+      if (probe(idx, n)) {
+        for (size_t t = 0; t < n; t++) valid[idx[t]] = 1;
+        return PASS;
+      }
     }
     if (n == 1) {
       valid[idx[0]] = 0;
-      return false;
+      return FAIL;
     }
     const size_t h = n / 2;
-    const bool left = solve(idx, h, false);
-    solve(idx + h, n - h, left);  // the left half passed: the right one holds the failure
-    return false;
+    const int left = solve(idx, h, false);
+    solve(idx + h, n - h, left == PASS);  // the left half passed: the right one holds the failure
+    return FAIL;
   }
 };
 }  // namespace
 
-int verify_many_combine(const VerifyManyIn& in, const F12* fixed_all, uint8_t* valid, zkmi_verify_stats* st) {
+int verify_many_combine_budget(const VerifyManyIn& in, const F12* fixed_all, uint64_t max_probes, uint8_t* valid,
+                               zkmi_verify_stats* st, std::vector<size_t>* undecided) {
   if (in.vk->ic.size() != in.n_inputs + 1) {
     zk::set_error("zkmi_groth16_verify_many: %zu public inputs for a key with %zu IC points", in.n_inputs,
                   in.vk->ic.size());
     return ZKMI_EINVAL;
   }
+  if (max_probes && !undecided) {
+    zk::set_error("zkmi_groth16_verify_many: a probe budget needs a list for the undecided proofs");
+    return ZKMI_EINVAL;
+  }
   int rc = verify_many_check_scalars(in.nb, in.n_inputs, in.inputs, in.rho);
   if (rc) return rc;
+  if (undecided) undecided->clear();
   std::vector<size_t> idx;
   for (size_t i = 0; i < in.nb; i++) {
     valid[i] = 0;
@@ -705,7 +730,7 @@ int verify_many_combine(const VerifyManyIn& in, const F12* fixed_all, uint8_t* v
   }
   if (st) st->invalid_points += in.nb - idx.size();
   if (idx.empty()) return 0;
-  Bisect bs{in, valid};
+  Bisect bs{in, valid, max_probes, undecided};
   bool all;
   if (fixed_all) {
     F12 f = *fixed_all;
@@ -721,6 +746,9 @@ int verify_many_combine(const VerifyManyIn& in, const F12* fixed_all, uint8_t* v
     bs.solve(idx.data(), idx.size(), true);
   if (st) st->final_exps += bs.probes;
   return 0;
+}
+int verify_many_combine(const VerifyManyIn& in, const F12* fixed_all, uint8_t* valid, zkmi_verify_stats* st) {
+  return verify_many_combine_budget(in, fixed_all, 0, valid, st, nullptr);
 }
 }  // namespace zkv
 

@@ -2,7 +2,8 @@
 // (pairing.hip) and with the stand-alone host checks under tests/host/: the
 // host Fq12 (F12), the two halves of the pairing check (Miller value, final
 // exponentiation), the decoded verifying key and the G1 helpers, plus the
-// combine-and-bisect routine of zkmi_groth16_verify_many.  Host code only.
+// combine-and-bisect routine of zkmi_groth16_verify_many and the constants of
+// the device final exponentiation.  Host code only.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -68,6 +69,11 @@ void f12_to_canon(uint64_t c[48], const F12& a);
 // contribute 1.  Miller values of disjoint pair sets multiply (f12_mul).
 F12 miller_value(const std::vector<G1>& ps, const std::vector<G2>& qs);
 bool final_exp_is_one(const F12& f);
+F12 f12_frob2(const F12& a);
+// The constants of final_exp_is_one for the device routine of pairing.h:
+// zeta^i (w^(q^2) = zeta w; 12 canonical Fq) and the exponent
+// (q^4 - q^2 + 1) / r, little-endian.
+void final_exp_constants(uint64_t zeta[48], uint64_t hard[12]);
 bool pairing_product_is_one(const std::vector<G1>& ps, const std::vector<G2>& qs);
 
 // ------------------------------------------------ batched verification
@@ -88,7 +94,8 @@ struct VerifyManyIn {
   const G1* rc;
 };
 // ZKMI_EINVAL for a zero weight or an input >= r (checked by the entry point
-// before any GPU work, and by verify_many_combine again)
+// before any GPU work, and by verify_many_combine again); rho = NULL checks
+// the inputs alone (verify_each has no weights)
 int verify_many_check_scalars(size_t nb, size_t n_inputs, const uint64_t* inputs, const uint64_t* rho);
 // The G1 sides of a subset's three fixed-G2 pairs:
 //   out = { -(sum rho_i) alpha, -sum rho_i X_i, -sum rho_i C_i },  i in idx,
@@ -100,5 +107,13 @@ void verify_many_fixed_g1(const VerifyManyIn& in, const size_t* idx, size_t n, G
 // number of bad[i] to *st (st may be NULL).  One final exponentiation when
 // the combined check holds; otherwise bisection, at most two probes a level.
 int verify_many_combine(const VerifyManyIn& in, const F12* fixed_all, uint8_t* valid, zkmi_verify_stats* st);
+// The same with a budget of final exponentiations (zkmi_ctx_set_verify_probes):
+// max_probes = 0 is verify_many_combine.  With max_probes >= 1 the first
+// combined check counts as a probe, no probe runs once max_probes have, and
+// the proofs that would have needed one come back in *undecided (ascending
+// within a subset; valid[i] = 0 for them until the caller decides them).
+// Decided and undecided proofs partition those with bad[i] == 0.
+int verify_many_combine_budget(const VerifyManyIn& in, const F12* fixed_all, uint64_t max_probes, uint8_t* valid,
+                               zkmi_verify_stats* st, std::vector<size_t>* undecided);
 
 }  // namespace zkv

@@ -99,6 +99,10 @@ struct zkmi_ctx {
   // proof job at submit; last_check holds the statuses of the job waited last
   int prove_check = 0;
   std::vector<zkmi_r1cs_status> last_check;
+  // probe budget of verify_many (zkmi_ctx_set_verify_probes; 0 = unlimited) and
+  // what the last call handed to the GPU: {gpu_decided, gpu_pairs, gpu_final_exps}
+  uint64_t verify_probes = 0;
+  uint64_t verify_last[3] = {0, 0, 0};
   // Stream budget: communicators alive on this context, and the
   // streams the library holds for it (context, lanes, communicators', witness
   // programs').  While a communicator exists the lanes are capped at

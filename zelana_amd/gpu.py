@@ -173,6 +173,15 @@ class Context:
     def prove_check(self) -> bool:
         return lib().zkmi_ctx_get_prove_check(self.h) == 1
 
+    def set_verify_probes(self, n: int):
+        """Probe budget of groth16_verify_many: 0 (default) = unlimited; n >= 1
+        = at most n host final exponentiations, then the undecided proofs get
+        exact verdicts on the GPU (groth16_verify_last reports them)."""
+        check(lib().zkmi_ctx_set_verify_probes(self.h, int(n)), "zkmi_ctx_set_verify_probes")
+
+    def get_verify_probes(self) -> int:
+        return int(lib().zkmi_ctx_get_verify_probes(self.h))
+
     def set_lanes(self, lanes: int):
         """MSM lanes (capped at 2 while a communicator exists: stream budget)."""
         check(lib().zkmi_msm_set_lanes(self.h, lanes))
@@ -579,14 +588,9 @@ def groth16_verify_many(ctx: Context, vk: VerifyingKey, proofs, inputs, rho=None
     non-zero ints < 2^128 fixes them (tests).  Returns ([bool per proof],
     {"pairs", "final_exps", "invalid_points"})."""
     nb = len(proofs)
-    if len(inputs) != nb or any(len(x) != vk.n_inputs for x in inputs):
-        raise ValueError(f"{nb} proofs need {nb} x {vk.n_inputs} public inputs")
+    a, b, c, ins = _proof_arrays(vk, proofs, inputs)
     if rho is not None and len(rho) != nb:
         raise ValueError("one weight per proof")
-    a = np.ascontiguousarray([np.asarray(p[0], np.uint64) for p in proofs], np.uint64).reshape(nb, 8)
-    b = np.ascontiguousarray([np.asarray(p[1], np.uint64) for p in proofs], np.uint64).reshape(nb, 16)
-    c = np.ascontiguousarray([np.asarray(p[2], np.uint64) for p in proofs], np.uint64).reshape(nb, 8)
-    ins = np.array([[_limbs(int(v)) for v in x] for x in inputs], np.uint64).reshape(nb, vk.n_inputs, 4)
     w = None
     if rho is not None:
         if any(not 0 <= int(v) < 1 << 128 for v in rho):
@@ -599,6 +603,41 @@ def groth16_verify_many(ctx: Context, vk: VerifyingKey, proofs, inputs, rho=None
           "zkmi_groth16_verify_many")
     return [bool(v) for v in valid[:nb]], {"pairs": int(st.pairs), "final_exps": int(st.final_exps),
                                            "invalid_points": int(st.invalid_points)}
+
+
+def _proof_arrays(vk, proofs, inputs):
+    nb = len(proofs)
+    if len(inputs) != nb or any(len(x) != vk.n_inputs for x in inputs):
+        raise ValueError(f"{nb} proofs need {nb} x {vk.n_inputs} public inputs")
+    a = np.ascontiguousarray([np.asarray(p[0], np.uint64) for p in proofs], np.uint64).reshape(nb, 8)
+    b = np.ascontiguousarray([np.asarray(p[1], np.uint64) for p in proofs], np.uint64).reshape(nb, 16)
+    c = np.ascontiguousarray([np.asarray(p[2], np.uint64) for p in proofs], np.uint64).reshape(nb, 8)
+    ins = np.array([[_limbs(int(v)) for v in x] for x in inputs], np.uint64).reshape(nb, vk.n_inputs, 4)
+    return a, b, c, ins
+
+
+def groth16_verify_each(ctx: Context, vk: VerifyingKey, proofs, inputs):
+    """zkmi_groth16_verify_each: exact per-proof verdicts, Miller loops and
+    final exponentiations on the GPU (no weights, no soundness error; the cost
+    does not depend on how many proofs are bad).  Arguments as
+    groth16_verify_many's.  Returns ([bool per proof], {"pairs", "final_exps",
+    "invalid_points"})."""
+    nb = len(proofs)
+    a, b, c, ins = _proof_arrays(vk, proofs, inputs)
+    valid = np.zeros(max(nb, 1), np.uint8)
+    st = VerifyStatsStruct()
+    check(lib().zkmi_groth16_verify_each(ctx.h, vk.h, nb, _p64(ins), _p64(a), _p64(b), _p64(c),
+                                         valid.ctypes.data_as(u8p), ctypes.byref(st)), "zkmi_groth16_verify_each")
+    return [bool(v) for v in valid[:nb]], {"pairs": int(st.pairs), "final_exps": int(st.final_exps),
+                                           "invalid_points": int(st.invalid_points)}
+
+
+def groth16_verify_last(ctx: Context) -> dict:
+    """zkmi_groth16_verify_last: what the last groth16_verify_many handed to
+    the GPU when its probe budget ran out (all 0 when it was not hit)."""
+    out = np.zeros(3, np.uint64)
+    check(lib().zkmi_groth16_verify_last(ctx.h, _p64(out)), "zkmi_groth16_verify_last")
+    return {"gpu_decided": int(out[0]), "gpu_pairs": int(out[1]), "gpu_final_exps": int(out[2])}
 
 
 def proof_to_alt_bn128_bytes(a, b, c) -> bytes:

@@ -316,16 +316,31 @@ class Groth16Prover:
         exponentiation for the batch, weights drawn by the library).
         public_inputs: one list of instance values per proof.  Proofs carrying
         only proof_bytes are decoded from them, as verify_pairing does."""
-        proofs = list(proofs)
+        return gpu.groth16_verify_many(self.ctx, self._resident_vk(), self._proof_points(proofs),
+                                       list(public_inputs))[0]
+
+    def verify_each(self, proofs, public_inputs) -> list:
+        """verify_pairing for a list of BatchProofs with an exact verdict per
+        proof from the GPU (zkmi_groth16_verify_each: Miller loops and final
+        exponentiations on the device, no weights; the cost does not depend on
+        how many proofs are bad).  Arguments and decoding as verify_many's."""
+        return gpu.groth16_verify_each(self.ctx, self._resident_vk(), self._proof_points(proofs),
+                                       list(public_inputs))[0]
+
+    def _resident_vk(self):
         if self._vk is None:
             self._vk = gpu.VerifyingKey(self.ctx, self.verifying_key)
+        return self._vk
+
+    @staticmethod
+    def _proof_points(proofs) -> list:
         pts = []
         for p in proofs:
             if p.a is None or p.b is None or p.c is None:
                 pts.append(proof_points_from_solana_bytes(p.proof_bytes))
             else:
                 pts.append((p.a, p.b, p.c))
-        return gpu.groth16_verify_many(self.ctx, self._vk, pts, list(public_inputs))[0]
+        return pts
 
     def verification_key_hash(self) -> bytes:
         return self.vk_hash
