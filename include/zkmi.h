@@ -569,6 +569,52 @@ uint64_t zkmi_ctx_get_verify_probes(const zkmi_ctx* ctx);
  * hit. */
 int zkmi_groth16_verify_last(zkmi_ctx* ctx, uint64_t out[3]);
 
+/* ------------------------------------------------- proofs from wire bytes
+ * The inverses of the proof encoders, and the batched verifiers over encoded
+ * proofs, decoded on the GPU (which has the decoding
+ * rule as a table).  A decoder tells two failures apart:
+ *   malformed      wrong length, unknown format, a coordinate >= q, a flag the
+ *                  format does not allow, a compressed x with no root
+ *   invalid point  a well-formed encoding of a point off the curve / twist, or
+ *                  of a B outside the order-r subgroup (the checks of
+ *                  zkmi_groth16_verify)
+ * Compressed: x < q after masking the two flag bits; bit 6 of the last byte =
+ * infinity and then every other bit, bit 7 included, is zero; otherwise y is
+ * the root selected by bit 7 (y > -y; Fq2 compares c1 first).  Every accepted
+ * 128-byte string re-serializes to itself.  Uncompressed: every coordinate
+ * < q after masking the point's last byte; bit 6 as above; bit 7 ignored; y
+ * as given.  SOLANA_LE / ALT_BN128_BE: no flag bits, every coordinate < q,
+ * all-zero = infinity, A's y comes back as q - y when y != 0: the exact
+ * inverses of the two encoders. */
+#define ZKMI_PROOF_ARK_COMPRESSED   0  /* 128 B: A32 | B64 | C32, SWFlags (zkmi_proof_serialize_compressed) */
+#define ZKMI_PROOF_ARK_UNCOMPRESSED 1  /* 256 B: A64 | B128 | C64, flags in each point's last byte */
+#define ZKMI_PROOF_SOLANA_LE        2  /* 256 B: -A | B | C little-endian, no flags (zkmi_proof_to_solana_bytes) */
+#define ZKMI_PROOF_ALT_BN128_BE     3  /* 256 B: -A | B | C big-endian, G2 as c1|c0 (zkmi_proof_to_alt_bn128_bytes) */
+size_t zkmi_proof_encoded_len(int fmt); /* 0 for an unknown fmt */
+/* One proof, on the host (no context).  0 and canonical affine points, or
+ * ZKMI_EINVAL (malformed) / ZKMI_EPOINT (invalid point) with a, b, c zeroed. */
+int zkmi_proof_decode(int fmt, const uint8_t* in, size_t len, uint64_t a[8], uint64_t b[16], uint64_t c[8]);
+/* nb proofs back to back (nb x zkmi_proof_encoded_len(fmt) bytes), decoded
+ * and validated on the GPU (context stream).  a / b / c: nb x 8 / 16 / 8 u64;
+ * status[i]: 0 ok, 1 malformed, 2 invalid point; the rows of a non-ok proof
+ * are zero.  Equals zkmi_proof_decode proof by proof. */
+int zkmi_proofs_decode(zkmi_ctx* ctx, int fmt, const uint8_t* proofs, size_t nb, uint64_t* a, uint64_t* b,
+                       uint64_t* c, uint8_t* status);
+/* zkmi_groth16_verify_many / _each over encoded proofs: the bytes are
+ * uploaded as they are and decoded by a kernel into the buffers the verify
+ * kernels read.  valid[i] is zkmi_groth16_verify's verdict on
+ * zkmi_proof_decode's points, 0 when that decode fails; malformed (nb bytes
+ * or NULL) is 1 for the proofs whose encoding is malformed, and those count in
+ * stats.invalid_points.  All argument rules of the point-taking calls hold
+ * (inputs >= r, nb = 0, a key of another context, rho, the probe budget and
+ * zkmi_groth16_verify_last); an unknown fmt is ZKMI_EINVAL. */
+int zkmi_groth16_verify_many_encoded(zkmi_ctx* ctx, const zkmi_vk* vk, int fmt, size_t nb, const uint8_t* proofs,
+                                     const uint64_t* inputs, const uint64_t* rho, uint8_t* valid, uint8_t* malformed,
+                                     zkmi_verify_stats* stats);
+int zkmi_groth16_verify_each_encoded(zkmi_ctx* ctx, const zkmi_vk* vk, int fmt, size_t nb, const uint8_t* proofs,
+                                     const uint64_t* inputs, uint8_t* valid, uint8_t* malformed,
+                                     zkmi_verify_each_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,18 @@ the same way; verify_many without a budget on that batch, timed ONCE (about
 extra final exponentiation, the figure the crossover is taken from); the host
 loop as above.  Against a library without verify_each (ZKMI_LIB pointing at an
 older build) only the unbudgeted and host figures are reported.
+
+    python tools/verify_many.py --encoded FMT [nb ...]
+
+FMT: compressed, uncompressed, solana, alt_bn128 or all.  Per nb and format, on
+the same proofs as wire bytes: zkmi_groth16_verify_many_encoded and
+_each_encoded (decoded on the GPU) against what a caller has without them, a
+host loop of zkmi_proof_decode followed by the point-taking call.  Both sides
+are timed at the C ABI (buffers and pointers prepared outside the timed
+region), alternated call by call in one run, warmed, median of VM_REPS calls
+(`*_spread_ms` = max - min).  `decode_loop_ms`: the host loop alone.
+`verify_decode_ms`: the decode kernels' time from three further calls with the
+profiler on.
 """
 import json
 import os
@@ -118,6 +130,79 @@ def each_mode(ctx, vk, vkb, base, base_in, nbs):
         print(json.dumps(row), flush=True)
 
 
+def encoded_mode(ctx, vk, base, base_in, nbs, fmts):
+    import ctypes
+
+    from zelana_amd import gpu
+    from zelana_amd._lib import VerifyStatsStruct, check, lib, u8p, u64p
+    L = lib()
+    enc = {gpu.PROOF_ARK_COMPRESSED: gpu.proof_serialize_compressed, gpu.PROOF_SOLANA_LE: gpu.proof_to_solana_bytes,
+           gpu.PROOF_ALT_BN128_BE: gpu.proof_to_alt_bn128_bytes}
+    names = {v: k for k, v in gpu.PROOF_FORMATS.items()}
+
+    def uncompressed(a, b, c):  # no encoder in the library: the compressed form's x, y as given, no flags
+        return b"".join(np.ascontiguousarray(p, "<u8").tobytes() for p in (a, b, c))
+
+    for nb in nbs:
+        ins = np.array([[[(base_in[i % 64][0] >> (64 * k)) & (2**64 - 1) for k in range(4)]] for i in range(nb)],
+                       np.uint64)
+        for fmt in fmts:
+            one = [enc.get(fmt, uncompressed)(*base[i]) for i in range(64)]
+            n = len(one[0])
+            buf = np.frombuffer(b"".join(one[i % 64] for i in range(nb)), np.uint8)
+            a, b, c = np.zeros((nb, 8), np.uint64), np.zeros((nb, 16), np.uint64), np.zeros((nb, 8), np.uint64)
+            valid, mal = np.zeros(nb, np.uint8), np.zeros(nb, np.uint8)
+            st = VerifyStatsStruct()
+            bp, ip, vp_, mp = buf.ctypes.data_as(u8p), ins.ctypes.data_as(u64p), valid.ctypes.data_as(u8p), \
+                mal.ctypes.data_as(u8p)
+            ap, bpp, cp = a.ctypes.data_as(u64p), b.ctypes.data_as(u64p), c.ctypes.data_as(u64p)
+            ptrs = [(ctypes.cast(buf.ctypes.data + n * i, u8p), ctypes.cast(a.ctypes.data + 64 * i, u64p),
+                     ctypes.cast(b.ctypes.data + 128 * i, u64p), ctypes.cast(c.ctypes.data + 64 * i, u64p))
+                    for i in range(nb)]
+
+            def decode_loop():
+                for r, pa, pb, pc in ptrs:
+                    if L.zkmi_proof_decode(fmt, r, n, pa, pb, pc):
+                        raise RuntimeError("a valid proof did not decode")
+
+            calls = {
+                "many_encoded": lambda: check(L.zkmi_groth16_verify_many_encoded(
+                    ctx.h, vk.h, fmt, nb, bp, ip, None, vp_, mp, ctypes.byref(st))),
+                "many_host_decode": lambda: (decode_loop(), check(L.zkmi_groth16_verify_many(
+                    ctx.h, vk.h, nb, ip, ap, bpp, cp, None, vp_, ctypes.byref(st)))),
+                "each_encoded": lambda: check(L.zkmi_groth16_verify_each_encoded(
+                    ctx.h, vk.h, fmt, nb, bp, ip, vp_, mp, ctypes.byref(st))),
+                "each_host_decode": lambda: (decode_loop(), check(L.zkmi_groth16_verify_each(
+                    ctx.h, vk.h, nb, ip, ap, bpp, cp, vp_, ctypes.byref(st)))),
+                "decode_loop": decode_loop,
+            }
+            times = {k: [] for k in calls}
+            for rep in range(REPS + 1):  # the first round warms
+                for k, fn in calls.items():
+                    valid[:] = 0
+                    t0 = time.perf_counter()
+                    fn()
+                    dt = 1e3 * (time.perf_counter() - t0)
+                    if k != "decode_loop":
+                        assert valid.all() and not mal.any(), k
+                    if rep:
+                        times[k].append(dt)
+            row = {"nb": nb, "fmt": names[fmt], "reps": REPS}
+            for k, t in times.items():
+                row[k + "_ms"] = round(statistics.median(t), 3)
+                row[k + "_spread_ms"] = round(max(t) - min(t), 3)
+            row["many_speedup"] = round(row["many_host_decode_ms"] / row["many_encoded_ms"], 3)
+            row["each_speedup"] = round(row["each_host_decode_ms"] / row["each_encoded_ms"], 3)
+            ctx.profile(True)
+            ctx.profile_reset()
+            for _ in range(3):
+                calls["many_encoded"]()
+            t, cnt = ctx.profile_get("verify_decode")
+            row["verify_decode_ms"] = round(t / max(cnt, 1), 4)
+            ctx.profile(False)
+            print(json.dumps(row), flush=True)
+
+
 def main():
     from zelana_amd import gpu
     from zelana_amd.keygen import circuit_specific_setup
@@ -125,6 +210,12 @@ def main():
     from zelana_amd.rng import StdRng
     args = sys.argv[1:]
     each = "--each" in args
+    fmts = None
+    if "--encoded" in args:
+        k = args.index("--encoded")
+        name = args[k + 1]
+        fmts = sorted(gpu.PROOF_FORMATS.values()) if name == "all" else [gpu.PROOF_FORMATS[name]]
+        del args[k:k + 2]
     nbs = [int(a) for a in args if a != "--each"] or [1, 64, 1024]
     ctx = gpu.Context(0)
     cs, _ = square_circuit(2)
@@ -140,6 +231,9 @@ def main():
         base_in.append([x * x % R])
     if each:
         each_mode(ctx, vk, vkb, base, base_in, nbs)
+        nbs = []
+    if fmts is not None:
+        encoded_mode(ctx, vk, base, base_in, nbs, fmts)
         nbs = []
     for nb in nbs:
         proofs = [base[i % 64] for i in range(nb)]

@@ -158,6 +158,13 @@ SIGNATURES = [
     ("zkmi_groth16_verify_last", ctypes.c_int, [vp, u64p]),
     ("zkmi_proof_to_solana_bytes", ctypes.c_int, [u64p, u64p, u64p, u8p]),
     ("zkmi_proof_serialize_compressed", ctypes.c_int, [u64p, u64p, u64p, u8p]),
+    ("zkmi_proof_encoded_len", sz, [ctypes.c_int]),
+    ("zkmi_proof_decode", ctypes.c_int, [ctypes.c_int, u8p, sz, u64p, u64p, u64p]),
+    ("zkmi_proofs_decode", ctypes.c_int, [vp, ctypes.c_int, u8p, sz, u64p, u64p, u64p, u8p]),
+    ("zkmi_groth16_verify_many_encoded", ctypes.c_int, [vp, vp, ctypes.c_int, sz, u8p, u64p, u64p, u8p, u8p,
+                                                        ctypes.POINTER(VerifyStatsStruct)]),
+    ("zkmi_groth16_verify_each_encoded", ctypes.c_int, [vp, vp, ctypes.c_int, sz, u8p, u64p, u8p, u8p,
+                                                        ctypes.POINTER(VerifyStatsStruct)]),
 ]
 
 

@@ -140,6 +140,48 @@ class ZBatchProver:
         self.wp.close()
 
 
+_R_LIMBS = np.array([(R >> (64 * k)) & (2**64 - 1) for k in range(4)], np.uint64)
+
+
+def verify_results(ctx: gpu.Context, vk: gpu.VerifyingKey, results, each: bool = False) -> list:
+    """The coordinator's check of the ProofResults it collected from its
+    workers (forge/crates/prover-coordinator/src/dispatcher.rs:290-384 settles
+    them unchecked): one bool per result, in order.  The proofs go to the GPU
+    as their 256 proof_bytes (zkmi_groth16_verify_many_encoded, or
+    _each_encoded with each=True) and are decoded there.
+
+    A result is False without reaching the GPU when its public_witness_bytes
+    are shorter than their header says, carry another count than the key's
+    inputs or a value >= r, or its proof_bytes are not 256 bytes: one garbled
+    result does not fail the call."""
+    n = vk.n_inputs
+    need = 12 + 32 * n
+    keep = [i for i, r in enumerate(results)
+            if len(r.proof_bytes) == 256 and len(r.public_witness_bytes) >= need
+            and struct.unpack(">I", bytes(r.public_witness_bytes[:4]))[0] == n]
+    out = [False] * len(results)
+    if not keep:
+        return out
+    # all witnesses at once: 32-byte big-endian values -> canonical little-endian limbs
+    pw = np.frombuffer(b"".join(bytes(results[i].public_witness_bytes[12:need]) for i in keep), ">u8")
+    ins = np.ascontiguousarray(pw.reshape(len(keep), n, 4)[:, :, ::-1], np.uint64)
+    lt = np.zeros(ins.shape[:2], bool)
+    eq = np.ones(ins.shape[:2], bool)
+    for k in (3, 2, 1, 0):
+        lt |= eq & (ins[:, :, k] < _R_LIMBS[k])
+        eq &= ins[:, :, k] == _R_LIMBS[k]
+    reduced = lt.all(axis=1)
+    sel = [j for j in range(len(keep)) if reduced[j]]
+    if not sel:
+        return out
+    fn = gpu.groth16_verify_each_encoded if each else gpu.groth16_verify_many_encoded
+    valid = fn(ctx, vk, gpu.PROOF_SOLANA_LE, [bytes(results[keep[j]].proof_bytes) for j in sel],
+               np.ascontiguousarray(ins[sel]))[0]
+    for j, v in zip(sel, valid):
+        out[keep[j]] = v
+    return out
+
+
 def parse_public_witness(data: bytes) -> list:
     """The worker's reading of public_witness_bytes (prover.rs:575-596): fewer
     than 12 bytes -> []; count = u32 BE of bytes 0..4; input i = "0x" + hex of

@@ -19,6 +19,7 @@
 
 #include "dev_io.h"
 #include "ec.h"
+#include "fq_sqrt.h"
 #include "r1cs_row.h"
 #include "zkmi_internal.h"
 
@@ -73,48 +74,10 @@ __device__ __forceinline__ bool lt_q_words(const uint32_t* w) {
   }
   return false;
 }
-// compare two fully reduced values limb-wise: -1, 0, 1
-__device__ __forceinline__ int fe_cmp(const Fe& a, const Fe& b) {
-  for (int i = NL - 1; i >= 0; i--) {
-    if (a.v[i] != b.v[i]) return a.v[i] > b.v[i] ? 1 : -1;
-  }
-  return 0;
-}
-__device__ Fe fq_pow64(const Fe& a, const uint64_t e[4]) { return pow<FqP>(a, e); }
-__device__ Fe2 f2_pow(const Fe2& a, const uint64_t e[4]) {
-  Fe2 r = f2_one();
-  for (int i = 255; i >= 0; i--) {
-    r = f2_sqr(r);
-    if ((e[i >> 6] >> (i & 63)) & 1) r = f2_mul(r, a);
-  }
-  return r;
-}
-__device__ bool f2_eq(const Fe2& a, const Fe2& b) { return eq<FqP>(a.c0, b.c0) && eq<FqP>(a.c1, b.c1); }
 // canonical (reduced, non-Montgomery) value of a Montgomery element
 __device__ Fe canon_q(const Fe& a) { return from_mont<FqP>(a); }
-
-// sqrt in Fq2 for q = 3 mod 4 (Adj & Rodriguez-Henriquez, Alg. 9); which root
-// is returned does not matter (the caller picks y or -y by the flag)
-__device__ bool f2_sqrt(const Fe2& a, Fe2& out) {
-  const uint64_t e34[4] = {0x4f082305b61f3f51ull, 0x65e05aa45a1c72a3ull, 0x6e14116da0605617ull,
-                           0x0c19139cb84c680aull};  // (q-3)/4
-  const uint64_t e12[4] = {0x9e10460b6c3e7ea3ull, 0xcbc0b548b438e546ull, 0xdc2822db40c0ac2eull,
-                           0x183227397098d014ull};  // (q-1)/2
-  Fe2 a1 = f2_pow(a, e34);
-  Fe2 alpha = f2_mul(a1, f2_mul(a1, a));
-  Fe2 conj = {alpha.c0, neg<FqP>(alpha.c1)};
-  Fe2 a0 = f2_mul(conj, alpha);
-  Fe2 m1 = {neg<FqP>(one<FqP>()), fe_zero()};
-  if (f2_eq(a0, m1)) return false;
-  Fe2 x0 = f2_mul(a1, a);
-  if (f2_eq(alpha, m1)) {
-    out = {neg<FqP>(x0.c1), x0.c0};
-  } else {
-    Fe2 b = {add<FqP>(alpha.c0, one<FqP>()), alpha.c1};
-    out = f2_mul(f2_pow(b, e12), x0);
-  }
-  return f2_eq(f2_sqr(out), a);
-}
+// (fe_cmp, f2_pow, f2_eq and the square roots fq_sqrt / f2_sqrt: fq_sqrt.h,
+// shared with the proof decoder of pairing.hip)
 
 // raw arkworks encodings (SWFlags in the top two bits of the last byte) ->
 // canonical affine words; bad |= 1 on any invalid point
@@ -140,10 +103,8 @@ __global__ void __launch_bounds__(256) k_decode_g1(const uint32_t* __restrict__ 
   Fe rhs = add<FqP>(mul<FqP>(sqr<FqP>(x), x), to_mont<FqP>(Fe{{3, 0, 0, 0, 0, 0, 0, 0, 0}}));
   Fe yc;
   if (compressed) {
-    const uint64_t e14[4] = {0x4f082305b61f3f52ull, 0x65e05aa45a1c72a3ull, 0x6e14116da0605617ull,
-                             0x0c19139cb84c680aull};  // (q+1)/4
-    Fe y = fq_pow64(rhs, e14);
-    if (!eq<FqP>(sqr<FqP>(y), rhs)) {
+    Fe y;
+    if (!fq_sqrt(rhs, y)) {
       atomicOr(bad, 1u);
       return;
     }

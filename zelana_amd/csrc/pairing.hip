@@ -13,6 +13,10 @@
 //                          the verdict, the only thing downloaded
 // which verify_many also uses for the proofs its bisection leaves undecided
 // once a probe budget (zkmi_ctx_set_verify_probes) is spent.
+// Both also take the proofs as wire bytes (zkmi_groth16_verify_*_encoded,
+// DESIGN.md §2.9):
+//   k_proof_decode / k_proof_decode_flag / k_proof_decode_fixed
+//                          the encodings -> the words the prepare kernels read
 #include <string.h>
 #include <sys/random.h>
 
@@ -21,6 +25,7 @@
 
 #include "dev_io.h"
 #include "pairing.h"
+#include "proof_decode.h"
 #include "verify_internal.h"
 #include "zkmi_internal.h"
 
@@ -390,7 +395,127 @@ __global__ void __launch_bounds__(VB) k_final_exp(const uint32_t* __restrict__ f
   valid[i] = final_exp_is_one(e2, e0, e1, fc->zeta, fc->hard) ? 1 : 0;
 }
 
+// ------------------------------------------------------------ encoded proofs
+// Proofs from their wire bytes (zkmi_groth16_verify_many_encoded / _each_encoded
+// / zkmi_proofs_decode): the encodings are uploaded as they are
+// and decoded by proof_decode.h into the d_a / d_b / d_c words that
+// k_verify_prepare / k_verify_each_prepare read.  A malformed proof gets
+// malformed[i] = 1 and ALL its words 0xFFFFFFFF, so v_validate rejects it
+// through v_lt_q and nothing downstream knows about encodings.
+
+// Compressed proofs (128 B: A 32 | B 64 | C 32), one lane per POINT, the two
+// Fq2 powers of the G2 square roots kept together in waves: lanes [0, nb) take
+// B, [nb, 2 nb) A, [2 nb, 3 nb) C, so a wave mixes G1 and G2 work only where
+// nb is no multiple of 64.  slot_bad[t] = 1 when lane t's point is malformed.
+__global__ void __launch_bounds__(VB) k_proof_decode(const uint32_t* __restrict__ raw, size_t nb,
+                                                     uint32_t* __restrict__ a, uint32_t* __restrict__ b,
+                                                     uint32_t* __restrict__ c, uint32_t* __restrict__ slot_bad) {
+  const size_t t = blockIdx.x * (size_t)VB + threadIdx.x;
+  if (t >= 3 * nb) return;
+  bool ok;
+  if (t < nb) {
+    ok = pd_g2_compressed(raw + t * 32 + 8, b + t * 32);
+  } else {
+    const bool is_c = t >= 2 * nb;
+    const size_t i = t - (is_c ? 2 * nb : nb);
+    ok = pd_g1_compressed(raw + i * 32 + (is_c ? 24 : 0), (is_c ? c : a) + i * 16);
+  }
+  slot_bad[t] = ok ? 0 : 1;
+}
+__device__ __forceinline__ void v_fill_malformed(size_t i, uint32_t* a, uint32_t* b, uint32_t* c) {
+  for (int k = 0; k < 16; k++) a[i * 16 + k] = c[i * 16 + k] = 0xFFFFFFFFu;
+  for (int k = 0; k < 32; k++) b[i * 32 + k] = 0xFFFFFFFFu;
+}
+// One lane per proof, after k_proof_decode: the three point flags of a proof
+// become its malformed byte and, when set, its words.
+__global__ void __launch_bounds__(VB) k_proof_decode_flag(const uint32_t* __restrict__ slot_bad, size_t nb,
+                                                          uint32_t* __restrict__ a, uint32_t* __restrict__ b,
+                                                          uint32_t* __restrict__ c, uint8_t* __restrict__ malformed) {
+  const size_t i = blockIdx.x * (size_t)VB + threadIdx.x;
+  if (i >= nb) return;
+  const bool bad = (slot_bad[i] | slot_bad[nb + i] | slot_bad[2 * nb + i]) != 0;
+  malformed[i] = bad ? 1 : 0;
+  if (bad) v_fill_malformed(i, a, b, c);
+}
+// The three 256-byte formats do no power: one lane per proof.
+template <int FMT>
+__global__ void __launch_bounds__(VB) k_proof_decode_fixed(const uint32_t* __restrict__ raw, size_t nb,
+                                                           uint32_t* __restrict__ a, uint32_t* __restrict__ b,
+                                                           uint32_t* __restrict__ c, uint8_t* __restrict__ malformed) {
+  const size_t i = blockIdx.x * (size_t)VB + threadIdx.x;
+  if (i >= nb) return;
+  const bool ok = pd_fixed<FMT>(raw + i * 64, a + i * 16, b + i * 32, c + i * 16);
+  malformed[i] = ok ? 0 : 1;
+  if (!ok) v_fill_malformed(i, a, b, c);
+}
+// One lane per proof: bad[i] = 1 when the decoded proof fails point validation
+// (v_validate), for zkmi_proofs_decode's status.
+__global__ void __launch_bounds__(VB) k_proof_validate(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                       const uint32_t* __restrict__ c, size_t nb,
+                                                       uint32_t* __restrict__ bad) {
+  const size_t i = blockIdx.x * (size_t)VB + threadIdx.x;
+  if (i >= nb) return;
+  uint32_t wa[16], wb[32], wc[16];
+#pragma unroll
+  for (int t = 0; t < 16; t++) wa[t] = a[i * 16 + t];
+#pragma unroll
+  for (int t = 0; t < 32; t++) wb[t] = b[i * 32 + t];
+#pragma unroll
+  for (int t = 0; t < 16; t++) wc[t] = c[i * 16 + t];
+  VPoints vp;
+  bad[i] = v_validate(wa, wb, wc, vp) ? 0 : 1;
+}
+
 static unsigned vblocks(size_t n) { return (unsigned)((n + VB - 1) / VB); }
+
+// Where a call's proofs come from: canonical points on the host (enc = NULL),
+// or nb encodings of format fmt, decoded on the device.  malformed: nb bytes
+// on the host or NULL; written by the time the context stream is next
+// synchronised.
+struct ProofSrc {
+  const uint64_t *a, *b, *c;
+  int fmt;
+  const uint8_t* enc;
+  uint8_t* malformed;
+};
+// d_a / d_b / d_c <- the proofs of src, on the context stream
+static int proofs_to_device(zkmi_ctx* ctx, const ProofSrc& src, size_t nb, uint32_t* d_a, uint32_t* d_b,
+                            uint32_t* d_c) {
+  if (!src.enc) {
+    ZK_HIP(hipMemcpyAsync(d_a, src.a, nb * 64, hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(d_b, src.b, nb * 128, hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(d_c, src.c, nb * 64, hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+  }
+  const size_t len = proof_encoded_len(src.fmt);
+  uint32_t *d_raw, *d_slot;
+  uint8_t* d_mal;
+  ZK_TRY(ctx->ws.get("vd_raw", nb * len, (void**)&d_raw));
+  ZK_TRY(ctx->ws.get("vd_slot", 3 * nb * 4, (void**)&d_slot));
+  ZK_TRY(ctx->ws.get("vd_mal", nb, (void**)&d_mal));
+  ZK_HIP(hipMemcpyAsync(d_raw, src.enc, nb * len, hipMemcpyHostToDevice, ctx->stream));
+  {
+    ScopedKernelTimer tm(ctx, "verify_decode");
+    const unsigned grid = vblocks(nb);  // one lane per proof
+    switch (src.fmt) {
+      case PROOF_ARK_COMPRESSED:
+        k_proof_decode<<<vblocks(3 * nb), VB, 0, ctx->stream>>>(d_raw, nb, d_a, d_b, d_c, d_slot);
+        k_proof_decode_flag<<<grid, VB, 0, ctx->stream>>>(d_slot, nb, d_a, d_b, d_c, d_mal);
+        break;
+      case PROOF_ARK_UNCOMPRESSED:
+        k_proof_decode_fixed<PROOF_ARK_UNCOMPRESSED><<<grid, VB, 0, ctx->stream>>>(d_raw, nb, d_a, d_b, d_c, d_mal);
+        break;
+      case PROOF_SOLANA_LE:
+        k_proof_decode_fixed<PROOF_SOLANA_LE><<<grid, VB, 0, ctx->stream>>>(d_raw, nb, d_a, d_b, d_c, d_mal);
+        break;
+      default:
+        k_proof_decode_fixed<PROOF_ALT_BN128_BE><<<grid, VB, 0, ctx->stream>>>(d_raw, nb, d_a, d_b, d_c, d_mal);
+    }
+  }
+  ZK_HIP(hipGetLastError());
+  if (src.malformed) ZK_HIP(hipMemcpyAsync(src.malformed, d_mal, nb, hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
+}
 
 // verify.cpp's Frobenius^2 constants and exponent, in the device's form
 static const FinalExpConst& final_exp_const() {
@@ -486,16 +611,14 @@ static int verify_each_run(zkmi_ctx* ctx, const zkmi_vk* vk, size_t n, const uin
   return timer_flush(ctx);
 }
 
-static int verify_each(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const uint64_t* a,
-                       const uint64_t* b, const uint64_t* c, uint8_t* valid, zkmi_verify_each_stats* stats) {
+static int verify_each(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const ProofSrc& src,
+                       uint8_t* valid, zkmi_verify_each_stats* stats) {
   const size_t n_in = vk->vk.ic.size() - 1;
   ZK_TRY(zkv::verify_many_check_scalars(nb, n_in, inputs, nullptr));
   uint32_t* d_in;
   ZK_TRY(ctx->ws.get("vm_in", nb * 68 * 4, (void**)&d_in));
   uint32_t *d_a = d_in, *d_b = d_a + nb * 16, *d_c = d_b + nb * 32;
-  ZK_HIP(hipMemcpyAsync(d_a, a, nb * 64, hipMemcpyHostToDevice, ctx->stream));
-  ZK_HIP(hipMemcpyAsync(d_b, b, nb * 128, hipMemcpyHostToDevice, ctx->stream));
-  ZK_HIP(hipMemcpyAsync(d_c, c, nb * 64, hipMemcpyHostToDevice, ctx->stream));
+  ZK_TRY(proofs_to_device(ctx, src, nb, d_a, d_b, d_c));
   uint64_t pairs, fexps, invalid;
   ZK_TRY(verify_each_run(ctx, vk, nb, d_a, d_b, d_c, nullptr, inputs, valid, &pairs, &fexps, &invalid));
   if (stats) *stats = {pairs, fexps, invalid};
@@ -519,9 +642,8 @@ static int draw_weights(uint64_t* w, size_t nb) {
   return 0;
 }
 
-static int verify_many(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const uint64_t* a,
-                       const uint64_t* b, const uint64_t* c, const uint64_t* rho_in, uint8_t* valid,
-                       zkmi_verify_stats* stats) {
+static int verify_many(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const ProofSrc& src,
+                       const uint64_t* rho_in, uint8_t* valid, zkmi_verify_stats* stats) {
   const size_t n_inputs = vk->vk.ic.size() - 1;
   std::vector<uint64_t> rho(2 * nb);
   if (rho_in)
@@ -537,9 +659,7 @@ static int verify_many(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64
   ZK_TRY(ctx->ws.get("vm_bad", nb * 4, (void**)&d_bad));
   ZK_TRY(ctx->ws.get("vm_f", np * F12_WORDS * 4, (void**)&d_f));
   uint32_t *d_a = d_in, *d_b = d_a + nb * 16, *d_c = d_b + nb * 32, *d_rho = d_c + nb * 16;
-  ZK_HIP(hipMemcpyAsync(d_a, a, nb * 64, hipMemcpyHostToDevice, ctx->stream));
-  ZK_HIP(hipMemcpyAsync(d_b, b, nb * 128, hipMemcpyHostToDevice, ctx->stream));
-  ZK_HIP(hipMemcpyAsync(d_c, c, nb * 64, hipMemcpyHostToDevice, ctx->stream));
+  ZK_TRY(proofs_to_device(ctx, src, nb, d_a, d_b, d_c));
   ZK_HIP(hipMemcpyAsync(d_rho, rho.data(), nb * 16, hipMemcpyHostToDevice, ctx->stream));
   {
     ScopedKernelTimer tm(ctx, "verify_prepare");
@@ -666,7 +786,7 @@ int zkmi_groth16_verify_many(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const 
     return ZKMI_EINVAL;
   }
   ZK_DEVICE_GUARD(ctx);
-  return verify_many(ctx, vk, nb, inputs, a, b, c, rho, valid, stats);
+  return verify_many(ctx, vk, nb, inputs, ProofSrc{a, b, c, 0, nullptr, nullptr}, rho, valid, stats);
 }
 
 int zkmi_groth16_verify_each(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const uint64_t* inputs, const uint64_t* a,
@@ -682,7 +802,95 @@ int zkmi_groth16_verify_each(zkmi_ctx* ctx, const zkmi_vk* vk, size_t nb, const 
     return ZKMI_EINVAL;
   }
   ZK_DEVICE_GUARD(ctx);
-  return verify_each(ctx, vk, nb, inputs, a, b, c, valid, stats);
+  return verify_each(ctx, vk, nb, inputs, ProofSrc{a, b, c, 0, nullptr, nullptr}, valid, stats);
+}
+
+int zkmi_groth16_verify_many_encoded(zkmi_ctx* ctx, const zkmi_vk* vk, int fmt, size_t nb, const uint8_t* proofs,
+                                     const uint64_t* inputs, const uint64_t* rho, uint8_t* valid, uint8_t* malformed,
+                                     zkmi_verify_stats* stats) {
+  if (!ctx || !vk || vk->ctx != ctx) {
+    set_error("zkmi_groth16_verify_many_encoded: null context or key, or a key of another context");
+    return ZKMI_EINVAL;
+  }
+  if (!proof_encoded_len(fmt)) {
+    set_error("zkmi_groth16_verify_many_encoded: unknown proof format %d", fmt);
+    return ZKMI_EINVAL;
+  }
+  if (stats) memset(stats, 0, sizeof(*stats));
+  ctx->verify_last[0] = ctx->verify_last[1] = ctx->verify_last[2] = 0;
+  if (nb == 0) return 0;
+  if (!proofs || !valid || (vk->vk.ic.size() > 1 && !inputs)) {
+    set_error("zkmi_groth16_verify_many_encoded: null argument");
+    return ZKMI_EINVAL;
+  }
+  ZK_DEVICE_GUARD(ctx);
+  return verify_many(ctx, vk, nb, inputs, ProofSrc{nullptr, nullptr, nullptr, fmt, proofs, malformed}, rho, valid,
+                     stats);
+}
+
+int zkmi_groth16_verify_each_encoded(zkmi_ctx* ctx, const zkmi_vk* vk, int fmt, size_t nb, const uint8_t* proofs,
+                                     const uint64_t* inputs, uint8_t* valid, uint8_t* malformed,
+                                     zkmi_verify_each_stats* stats) {
+  if (!ctx || !vk || vk->ctx != ctx) {
+    set_error("zkmi_groth16_verify_each_encoded: null context or key, or a key of another context");
+    return ZKMI_EINVAL;
+  }
+  if (!proof_encoded_len(fmt)) {
+    set_error("zkmi_groth16_verify_each_encoded: unknown proof format %d", fmt);
+    return ZKMI_EINVAL;
+  }
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (nb == 0) return 0;
+  if (!proofs || !valid || (vk->vk.ic.size() > 1 && !inputs)) {
+    set_error("zkmi_groth16_verify_each_encoded: null argument");
+    return ZKMI_EINVAL;
+  }
+  ZK_DEVICE_GUARD(ctx);
+  return verify_each(ctx, vk, nb, inputs, ProofSrc{nullptr, nullptr, nullptr, fmt, proofs, malformed}, valid, stats);
+}
+
+int zkmi_proofs_decode(zkmi_ctx* ctx, int fmt, const uint8_t* proofs, size_t nb, uint64_t* a, uint64_t* b,
+                       uint64_t* c, uint8_t* status) {
+  if (!ctx) {
+    set_error("zkmi_proofs_decode: null context");
+    return ZKMI_EINVAL;
+  }
+  if (!proof_encoded_len(fmt)) {
+    set_error("zkmi_proofs_decode: unknown proof format %d", fmt);
+    return ZKMI_EINVAL;
+  }
+  if (nb == 0) return 0;
+  if (!proofs || !a || !b || !c || !status) {
+    set_error("zkmi_proofs_decode: null argument");
+    return ZKMI_EINVAL;
+  }
+  ZK_DEVICE_GUARD(ctx);
+  uint32_t *d_in, *d_bad;
+  ZK_TRY(ctx->ws.get("vm_in", nb * 68 * 4, (void**)&d_in));
+  ZK_TRY(ctx->ws.get("vd_bad", nb * 4, (void**)&d_bad));
+  uint32_t *d_a = d_in, *d_b = d_a + nb * 16, *d_c = d_b + nb * 32;
+  std::vector<uint8_t> mal(nb);
+  ZK_TRY(proofs_to_device(ctx, ProofSrc{nullptr, nullptr, nullptr, fmt, proofs, mal.data()}, nb, d_a, d_b, d_c));
+  {
+    ScopedKernelTimer tm(ctx, "verify_decode_validate");
+    k_proof_validate<<<vblocks(nb), VB, 0, ctx->stream>>>(d_a, d_b, d_c, nb, d_bad);
+  }
+  ZK_HIP(hipGetLastError());
+  std::vector<uint32_t> bad32(nb);
+  ZK_HIP(hipMemcpyAsync(bad32.data(), d_bad, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(a, d_a, nb * 64, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(b, d_b, nb * 128, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(c, d_c, nb * 64, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  ZK_TRY(timer_flush(ctx));
+  for (size_t i = 0; i < nb; i++) {
+    status[i] = mal[i] ? 1 : bad32[i] ? 2 : 0;
+    if (!status[i]) continue;
+    memset(a + 8 * i, 0, 64);
+    memset(b + 16 * i, 0, 128);
+    memset(c + 8 * i, 0, 64);
+  }
+  return 0;
 }
 
 int zkmi_ctx_set_verify_probes(zkmi_ctx* ctx, uint64_t max_probes) {

@@ -249,7 +249,8 @@ int f2_cmp(const F2& a, const F2& b) {
   int c = cmp_canon(a.c1, b.c1);
   return c ? c : cmp_canon(a.c0, b.c0);
 }
-bool g2_decompress(const uint8_t in[64], G2* out) {
+// the twist point of a compressed encoding, before the subgroup check
+bool g2_decompress_twist(const uint8_t in[64], G2* out) {
   const bool pos = in[63] & 0x80, infl = in[63] & 0x40;
   uint64_t x0[4], x1[4];
   le_words(x0, in);
@@ -266,10 +267,10 @@ bool g2_decompress(const uint8_t in[64], G2* out) {
   if (!fq2_sqrt(f2_add(f2_mul(f2_mul(p.x, p.x), p.x), twist_b()), &p.y)) return false;
   F2 ny = HFq2::neg(p.y);
   if ((f2_cmp(p.y, ny) > 0) != pos) p.y = ny;
-  if (!g2_in_subgroup(p)) return false;
   *out = p;
   return true;
 }
+bool g2_decompress(const uint8_t in[64], G2* out) { return g2_decompress_twist(in, out) && g2_in_subgroup(*out); }
 
 // ------------------------------------------------------------- Fq12
 F12 f12_one() {
@@ -595,6 +596,63 @@ void f12_to_canon(uint64_t c[48], const F12& a) {
   for (int i = 0; i < 12; i++) to_canon(c + 4 * i, a.c[i]);
 }
 
+// ------------------------------------------------------- proof decoding
+// The inverses of the four proof encoders (zkmi.h "proofs from wire bytes",
+// DESIGN.md section 2.9).  0 = well-formed (a / b / c canonical, all-zero =
+// infinity; the points themselves not yet validated), 1 = malformed.
+static bool canon_zero(const uint64_t* c, int n) {
+  uint64_t o = 0;
+  for (int i = 0; i < n; i++) o |= c[i];
+  return o == 0;
+}
+static void canon_neg_q(uint64_t c[4]) {
+  if (!canon_zero(c, 4)) sub4(c, QP, c);
+}
+// one arkworks-uncompressed point of nc coordinates: flags in the last byte
+static bool point_uncompressed(const uint8_t* in, int nc, uint64_t* out) {
+  const uint8_t last = in[32 * nc - 1];
+  for (int k = 0; k < nc; k++) le_words(out + 4 * k, in + 32 * k);
+  out[4 * nc - 1] &= 0x3FFFFFFFFFFFFFFFULL;
+  if (last & 0x40) return !(last & 0x80) && canon_zero(out, 4 * nc);  // infinity: nothing else set
+  for (int k = 0; k < nc; k++)
+    if (!lt_q(out + 4 * k)) return false;
+  return true;  // bit 7 is ignored: y is given
+}
+int proof_decode_words(int fmt, const uint8_t* in, uint64_t a[8], uint64_t b[16], uint64_t c[8]) {
+  if (fmt == ZKMI_PROOF_ARK_COMPRESSED) {
+    G1 A, C;
+    G2 B;
+    if (!g1_decompress(in, &A) || !g2_decompress_twist(in + 32, &B) || !g1_decompress(in + 96, &C)) return 1;
+    g1_to_canon(a, A);
+    g2_to_canon(b, B);
+    g1_to_canon(c, C);
+    return 0;
+  }
+  if (fmt == ZKMI_PROOF_ARK_UNCOMPRESSED)
+    return point_uncompressed(in, 2, a) && point_uncompressed(in + 64, 4, b) && point_uncompressed(in + 192, 2, c)
+               ? 0
+               : 1;
+  const bool be = fmt == ZKMI_PROOF_ALT_BN128_BE;
+  uint64_t w[8][4];
+  for (int k = 0; k < 8; k++) {
+    if (be)
+      get_be(w[k], in + 32 * k);
+    else
+      le_words(w[k], in + 32 * k);
+    if (!lt_q(w[k])) return 1;
+  }
+  canon_neg_q(w[1]);  // the encoders store -A
+  memcpy(a, w[0], 64);
+  memcpy(c, w[6], 64);
+  for (int k = 0; k < 4; k++) memcpy(b + 4 * (be ? k ^ 1 : k), w[2 + k], 32);  // big-endian G2: c1 | c0
+  return 0;
+}
+// the point checks of zkmi_groth16_verify on canonical words (< q each)
+bool proof_points_valid(const uint64_t a[8], const uint64_t b[16], const uint64_t c[8]) {
+  const G2 B = g2_from_canon(b);
+  return g1_on_curve(g1_from_canon(a)) && g1_on_curve(g1_from_canon(c)) && g2_on_curve(B) && g2_in_subgroup(B);
+}
+
 // ------------------------------------------------- batched verification
 // (sum of 128 x 256-bit products) mod r, by plain long arithmetic: the sums
 // are a few hundred word operations per public input, far off any hot path
@@ -799,6 +857,40 @@ int zkmi_groth16_verify(const uint8_t* vk_bytes, size_t vk_len, const uint64_t* 
   // e(A, B) e(-alpha, beta) e(-vk_x, gamma) e(-C, delta) == 1
   *valid = pairing_product_is_one({A, neg(vk.alpha), neg(acc), neg(C)}, {B, vk.beta, vk.gamma, vk.delta}) ? 1 : 0;
   return 0;
+}
+
+size_t zkmi_proof_encoded_len(int fmt) {
+  if (fmt == ZKMI_PROOF_ARK_COMPRESSED) return 128;
+  return fmt >= ZKMI_PROOF_ARK_UNCOMPRESSED && fmt <= ZKMI_PROOF_ALT_BN128_BE ? 256 : 0;
+}
+
+int zkmi_proof_decode(int fmt, const uint8_t* in, size_t len, uint64_t a[8], uint64_t b[16], uint64_t c[8]) {
+  if (!in || !a || !b || !c) {
+    set_error("zkmi_proof_decode: null argument");
+    return ZKMI_EINVAL;
+  }
+  memset(a, 0, 64);
+  memset(b, 0, 128);
+  memset(c, 0, 64);
+  const size_t want = zkmi_proof_encoded_len(fmt);
+  if (!want || len != want) {
+    set_error("zkmi_proof_decode: format %d takes %zu bytes, got %zu", fmt, want, len);
+    return ZKMI_EINVAL;
+  }
+  int rc = 0;
+  if (proof_decode_words(fmt, in, a, b, c)) {
+    set_error("zkmi_proof_decode: malformed encoding");
+    rc = ZKMI_EINVAL;
+  } else if (!proof_points_valid(a, b, c)) {
+    set_error("zkmi_proof_decode: a point off the curve or outside the subgroup");
+    rc = ZKMI_EPOINT;
+  }
+  if (rc) {
+    memset(a, 0, 64);
+    memset(b, 0, 128);
+    memset(c, 0, 64);
+  }
+  return rc;
 }
 
 int zkmi_alt_bn128_pairing(const uint8_t* input, size_t len, uint8_t out[32]) {

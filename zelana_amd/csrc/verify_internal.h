@@ -54,6 +54,13 @@ G1 g1_neg(G1 p);
 // sum of pts[i] over idx (one inversion for the whole sum)
 G1 g1_sum(const G1* pts, const size_t* idx, size_t n);
 bool vk_decode(const uint8_t* b, size_t len, Vk* vk, const char** why);
+// One encoded proof (fmt: ZKMI_PROOF_*, in: zkmi_proof_encoded_len(fmt) bytes)
+// -> canonical words by the rule of DESIGN.md section 2.9: 0, or 1 when the
+// encoding is malformed.  The points are not validated: proof_points_valid
+// applies zkmi_groth16_verify's checks (on the curve / twist, B in the
+// subgroup) to well-formed words.
+int proof_decode_words(int fmt, const uint8_t* in, uint64_t a[8], uint64_t b[16], uint64_t c[8]);
+bool proof_points_valid(const uint64_t a[8], const uint64_t b[16], const uint64_t c[8]);
 
 F12 f12_one();
 F12 f12_mul(const F12& a, const F12& b);

@@ -665,6 +665,119 @@ def proof_serialize_compressed(a, b, c) -> bytes:
     return out.tobytes()
 
 
+PROOF_ARK_COMPRESSED, PROOF_ARK_UNCOMPRESSED, PROOF_SOLANA_LE, PROOF_ALT_BN128_BE = 0, 1, 2, 3  # ZKMI_PROOF_*
+PROOF_FORMATS = {"compressed": PROOF_ARK_COMPRESSED, "uncompressed": PROOF_ARK_UNCOMPRESSED,
+                 "solana": PROOF_SOLANA_LE, "alt_bn128": PROOF_ALT_BN128_BE}
+
+
+class ProofDecodeError(ValueError):
+    """proof_decode: status 1 = malformed encoding, 2 = a well-formed encoding
+    of an invalid point (off the curve / twist, or B outside the subgroup)."""
+
+    def __init__(self, status: int, msg: str):
+        super().__init__(msg)
+        self.status = status
+
+
+def proof_encoded_len(fmt: int) -> int:
+    n = int(lib().zkmi_proof_encoded_len(fmt))
+    if not n:
+        raise ValueError(f"unknown proof format {fmt}")
+    return n
+
+
+def _encoded(fmt: int, raws):
+    """bytes (nb encodings back to back) or a list of bytes -> (u8 array, nb)"""
+    n = proof_encoded_len(fmt)
+    if isinstance(raws, (bytes, bytearray, memoryview)):
+        buf = bytes(raws)
+        if len(buf) % n:
+            raise ValueError(f"{len(buf)} bytes are no whole number of {n}-byte proofs")
+    else:
+        raws = [bytes(r) for r in raws]
+        if any(len(r) != n for r in raws):
+            raise ValueError(f"every proof of format {fmt} takes {n} bytes")
+        buf = b"".join(raws)
+    return np.frombuffer(buf, np.uint8), len(buf) // n
+
+
+def proof_decode(fmt: int, raw: bytes):
+    """zkmi_proof_decode (host): one encoded proof -> canonical (a, b, c).
+    Raises ProofDecodeError (status 1 malformed, wrong length included; 2
+    invalid point)."""
+    buf = np.frombuffer(bytes(raw), np.uint8)
+    a, b, c = np.zeros(8, np.uint64), np.zeros(16, np.uint64), np.zeros(8, np.uint64)
+    rc = lib().zkmi_proof_decode(fmt, buf.ctypes.data_as(u8p), buf.size, _p64(a), _p64(b), _p64(c))
+    if rc:
+        status = 2 if rc == -5 else 1  # ZKMI_EPOINT: an invalid point; anything else: malformed
+        raise ProofDecodeError(status, lib().zkmi_last_error().decode(errors="replace"))
+    return a, b, c
+
+
+def proofs_decode(ctx: Context, fmt: int, raws):
+    """zkmi_proofs_decode: encoded proofs (bytes back to back, or a list of
+    bytes) decoded and validated on the GPU.  Returns (a[nb, 8], b[nb, 16],
+    c[nb, 8], status[nb]): status 0 ok, 1 malformed, 2 invalid point; the rows
+    of a non-ok proof are zero."""
+    buf, nb = _encoded(fmt, raws)
+    a, b, c = np.zeros((nb, 8), np.uint64), np.zeros((nb, 16), np.uint64), np.zeros((nb, 8), np.uint64)
+    status = np.zeros(max(nb, 1), np.uint8)
+    check(lib().zkmi_proofs_decode(ctx.h, fmt, buf.ctypes.data_as(u8p), nb, _p64(a), _p64(b), _p64(c),
+                                   status.ctypes.data_as(u8p)), "zkmi_proofs_decode")
+    return a, b, c, status[:nb]
+
+
+def _input_array(vk, nb, inputs):
+    """one list of ints per proof, or canonical limbs already (nb, n_inputs, 4) u64"""
+    if isinstance(inputs, np.ndarray):
+        ins = np.ascontiguousarray(inputs, np.uint64)
+        if ins.shape != (nb, vk.n_inputs, 4):
+            raise ValueError(f"{nb} proofs need public inputs of shape ({nb}, {vk.n_inputs}, 4)")
+        return ins
+    if len(inputs) != nb or any(len(x) != vk.n_inputs for x in inputs):
+        raise ValueError(f"{nb} proofs need {nb} x {vk.n_inputs} public inputs")
+    return np.array([[_limbs(int(v)) for v in x] for x in inputs], np.uint64).reshape(nb, vk.n_inputs, 4)
+
+
+def _stats(st) -> dict:
+    return {"pairs": int(st.pairs), "final_exps": int(st.final_exps), "invalid_points": int(st.invalid_points)}
+
+
+def groth16_verify_many_encoded(ctx: Context, vk: VerifyingKey, fmt: int, raws, inputs, rho=None):
+    """zkmi_groth16_verify_many_encoded: groth16_verify_many over encoded
+    proofs (bytes back to back, or a list of bytes), decoded on the GPU.
+    inputs: one list of ints per proof, or a (nb, n_inputs, 4) u64 array of
+    canonical limbs.  Returns ([bool per proof], [malformed per proof], stats);
+    a malformed proof is False and counts in stats["invalid_points"]."""
+    buf, nb = _encoded(fmt, raws)
+    ins = _input_array(vk, nb, inputs)
+    w = None
+    if rho is not None:
+        if len(rho) != nb or any(not 0 <= int(v) < 1 << 128 for v in rho):
+            raise ValueError("one 128-bit weight per proof")
+        w = np.array([[int(v) & (2**64 - 1), int(v) >> 64] for v in rho], np.uint64).reshape(nb, 2)
+    valid, mal = np.zeros(max(nb, 1), np.uint8), np.zeros(max(nb, 1), np.uint8)
+    st = VerifyStatsStruct()
+    check(lib().zkmi_groth16_verify_many_encoded(ctx.h, vk.h, fmt, nb, buf.ctypes.data_as(u8p), _p64(ins),
+                                                 None if w is None else _p64(w), valid.ctypes.data_as(u8p),
+                                                 mal.ctypes.data_as(u8p), ctypes.byref(st)),
+          "zkmi_groth16_verify_many_encoded")
+    return [bool(v) for v in valid[:nb]], [bool(v) for v in mal[:nb]], _stats(st)
+
+
+def groth16_verify_each_encoded(ctx: Context, vk: VerifyingKey, fmt: int, raws, inputs):
+    """zkmi_groth16_verify_each_encoded: groth16_verify_each over encoded
+    proofs; arguments and results as groth16_verify_many_encoded's."""
+    buf, nb = _encoded(fmt, raws)
+    ins = _input_array(vk, nb, inputs)
+    valid, mal = np.zeros(max(nb, 1), np.uint8), np.zeros(max(nb, 1), np.uint8)
+    st = VerifyStatsStruct()
+    check(lib().zkmi_groth16_verify_each_encoded(ctx.h, vk.h, fmt, nb, buf.ctypes.data_as(u8p), _p64(ins),
+                                                 valid.ctypes.data_as(u8p), mal.ctypes.data_as(u8p),
+                                                 ctypes.byref(st)), "zkmi_groth16_verify_each_encoded")
+    return [bool(v) for v in valid[:nb]], [bool(v) for v in mal[:nb]], _stats(st)
+
+
 class R1CSDevice:
     """Circuit matrices resident in HBM (zkmi_r1cs_create)."""
 

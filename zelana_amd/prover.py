@@ -357,6 +357,24 @@ class Groth16Prover:
         raw = gpu.proof_serialize_compressed(proof.a, proof.b, proof.c)
         return json.dumps({"proof": base64.b64encode(raw).decode()}, indent=2)
 
+    @staticmethod
+    def import_proof_json(text: str, inputs: BatchPublicInputs) -> BatchProof:
+        """The inverse of export_proof_json: the l2_proof.json text (base64 of
+        the 128-B compressed arkworks Proof) back into a BatchProof for
+        `inputs`, decoded and validated by zkmi_proof_decode.  Raises
+        gpu.ProofDecodeError for a malformed encoding or an invalid point."""
+        raw = base64.b64decode(json.loads(text)["proof"], validate=True)
+        a, b, c = gpu.proof_decode(gpu.PROOF_ARK_COMPRESSED, raw)
+        return BatchProof(inputs, gpu.proof_to_solana_bytes(a, b, c), 0, a, b, c)
+
+    def verify_many_encoded(self, fmt: int, raws, public_inputs, each: bool = False) -> list:
+        """verify_many (each=False) or verify_each (each=True) for proofs held
+        as wire bytes of format fmt (gpu.PROOF_*; bytes back to back or a list
+        of bytes), decoded on the GPU: no per-proof host work.  A malformed
+        proof is False, like one that does not verify."""
+        fn = gpu.groth16_verify_each_encoded if each else gpu.groth16_verify_many_encoded
+        return fn(self.ctx, self._resident_vk(), fmt, raws, public_inputs)[0]
+
     def export_vk_json(self) -> str:
         return json.dumps({"verifying_key": base64.b64encode(self.verifying_key).decode()}, indent=2)
 
