@@ -421,11 +421,35 @@ int zkmi_proof_serialize_compressed(const uint64_t a[8], const uint64_t b[16], c
  *         x^4, x^5 of every S-box in round order (round 0 only for masked
  *         elements): 3 popcount(mask) + 231 values.  Reads the round
  *         constants ark[r][i] at coefficient 3r + i and the MDS matrix
- *         m[i][j] at 192 + 3i + j (so num_coeffs >= 201)
+ *         m[i][j] at 192 + 3i + j (so num_coeffs >= 201);
+ *         9 POSEIDON_RC kind 7's op with the round counts in the op (for
+ *         ShieldedTransferCircuit's sponge, prover/src/circuit/shielded.rs:
+ *         365-368: 8 full + 57 partial rounds).  b_off holds: bits 0-15 the
+ *         third combination's length, bits 16-18 the mask (1..7), bits 19-26
+ *         R_p, bits 27-31 R_f / 2 (>= 1; R_f + R_p <= 72).  Combinations,
+ *         quad mapping and trace order as kind 7; out: 3 popcount(mask) +
+ *         9 (R_f/2 - 1) + 3 R_p + 9 R_f/2 values (3 popcount(mask) + 234 for
+ *         8 + 57).  Reads ark[r][i] at coefficient 3r + i and m[i][j] at
+ *         3 (R_f + R_p) + 3i + j (so num_coeffs >= 3 (R_f + R_p) + 9).  Every
+ *         kind-9 op of a program has the same R_f and R_p, and a program
+ *         holds kind 7 or kind 9 ops, not both (either table starts at
+ *         coefficient 0);
+ *         10 SELECT z[out] = <c,z> != 0 ? <t,z> : <f,z> (r1cs-std
+ *         AllocatedFp::conditionally_select's witness): c, t, f stored back to
+ *         back at a_off, of lengths a_len, b_len and b_off & 0xFFFF (b_off's
+ *         upper bits 0).
+ *         Of a kind 7 / 9 trace only the last round's three x^5 may be read
+ *         by other ops (the rest stays in Montgomery form until the run's
+ *         last kernel).
  *   term: 2 x u32 {z index, coefficient index}; <a,z> = sum over
  *         term[a_off .. a_off + a_len) of coeff * z
  *   levels: ops [level_start[l], level_start[l+1]) depend only on inputs and
- *         earlier levels. */
+ *         earlier levels.  A level is one launch, except runs of small levels
+ *         (<= 256 ops each) without permutations, and runs of small levels
+ *         made of kinds 9 and 10 alone, which one workgroup steps through
+ *         in one launch (ZKMI_DEBUG_WPROG_NO_RC_CHAIN=1 in the environment
+ *         of zkmi_wprog_create turns the second kind of run off: a
+ *         measurement switch). */
 typedef struct zkmi_wprog zkmi_wprog;
 typedef struct {
   size_t num_vars;                             /* |z| */

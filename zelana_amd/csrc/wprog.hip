@@ -23,6 +23,12 @@
 //          x^5, 8 full + 56 partial rounds, Grain-LFSR constants): state in =
 //          three combinations, out = every S-box's x^2, x^4, x^5 in round
 //          order (round 0 skips constant elements, per the op's mask)
+// and, for ShieldedTransferCircuit (prover/src/circuit/shielded.rs:142-368,
+// recorded by the Python synthesizer, zelana_amd/shielded.py):
+//   POSEIDON_RC  POSEIDON with the round counts in the op (that circuit's
+//          sponge has 8 full + 57 partial rounds, shielded.rs:365-368) and
+//          the constant table laid out for them
+//   SELECT z[out] = <c, z> != 0 ? <t, z> : <f, z>  (conditionally_select)
 // and each level is one launch; a batch uploads only its inputs.
 //
 // The program is latency-bound, not throughput-bound: its critical path is
@@ -40,6 +46,7 @@
 // per SIMD, the mad latency it hides by splitting columns matters more than
 // the add it costs (the opposite trade of the throughput kernels).
 #define ZK_NO_ASM_MAD 1
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -53,7 +60,7 @@
 namespace zk {
 
 constexpr int WP_MUL = 1, WP_INV = 2, WP_BITS64 = 3, WP_PERM = 4, WP_BITS = 5, WP_NZ = 6, WP_POSEIDON = 7,
-              WP_INV1 = 8;
+              WP_INV1 = 8, WP_POSEIDON_RC = 9, WP_SELECT = 10;
 constexpr int MIMC_R = 91;
 // Poseidon (get_poseidon_config): constants at coefficient ids 3 r + i (ark)
 // and 192 + 3 i + j (MDS) of the program's table (zkmi.h)
@@ -61,6 +68,22 @@ constexpr int POS_ROUNDS = 64, POS_FULL_HALF = 4, POS_NCONST = 201;
 __host__ __device__ constexpr uint32_t poseidon_trace_len(uint32_t mask) {
   return 3 * ((mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1)) + 231;
 }
+// POSEIDON_RC: R_f / 2 and R_p in the op's word 3 (bits 27-31, 19-26; mask in
+// bits 16-18); constants at 3 r + i (ark) and 3 (R_f + R_p) + 3 i + j (MDS).
+// The LDS table of the kernel variant that runs them holds POS_RC_MAX_ROUNDS
+// rounds' constants.
+constexpr int POS_RC_MAX_ROUNDS = 72, POS_RC_MAX_NCONST = 3 * POS_RC_MAX_ROUNDS + 9;
+__host__ __device__ constexpr uint32_t pos_rc_mask(uint32_t w) { return (w >> 16) & 7; }
+__host__ __device__ constexpr uint32_t pos_rc_partial(uint32_t w) { return (w >> 19) & 0xFF; }
+__host__ __device__ constexpr uint32_t pos_rc_half(uint32_t w) { return w >> 27; }
+__host__ __device__ constexpr uint32_t pos_rc_trace_len(uint32_t w) {
+  const uint32_t mask = pos_rc_mask(w);
+  return 3 * ((mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1)) + 9 * (pos_rc_half(w) - 1) + 3 * pos_rc_partial(w) +
+         9 * pos_rc_half(w);
+}
+// which wprog_op variant a kernel instance holds: no Poseidon, kind 7, kind 9
+constexpr int POS_NONE = 0, POS_L2 = 1, POS_RC = 2;
+constexpr uint8_t LV_RC = 1, LV_SELECT = 2, LV_LEAN = 4;  // zkmi_wprog::level_flags
 
 // a * 2^-261 mod r for a < 2^261 with normalised limbs: Montgomery reduction
 // alone (a product with 1 without its 81 product mads)
@@ -315,8 +338,13 @@ __device__ __forceinline__ Fe sel(bool c, const Fe& a, const Fe& b) {
 // form); each round adds its constant, S-boxes (all lanes in full rounds,
 // lane 0 in partial ones; the S-boxing lane stores x^2, x^4, x^5), then every
 // lane forms its MDS row from the three elements (DPP quad broadcasts).
+// RC: the round counts come from the op (POSEIDON_RC: half = R_f / 2, rounds
+// = R_f + R_p); otherwise they are L2BlockCircuit's, compiled in.
+template <bool RC>
 __device__ __forceinline__ void poseidon_quad(const Fe& in, uint32_t q, uint32_t out, uint32_t mask,
-                                              const Fe* __restrict__ pc, uint32_t* __restrict__ z) {
+                                              const Fe* __restrict__ pc, uint32_t* __restrict__ z, int rc_half,
+                                              int rc_rounds) {
+  const int POS_ROUNDS = RC ? rc_rounds : zk::POS_ROUNDS, POS_FULL_HALF = RC ? rc_half : zk::POS_FULL_HALF;
   const uint32_t qq = q < 3 ? q : 2;
   Fe s = mul<FrP>(in, fe_const<FrP>(FrP::R2));
   const uint32_t m0 = 3 * __builtin_popcount(mask);  // trace values of round 0
@@ -335,9 +363,10 @@ __device__ __forceinline__ void poseidon_quad(const Fe& in, uint32_t q, uint32_t
       } else if (r < POS_FULL_HALF) {
         at = m0 + 9 * (r - 1) + 3 * q;
       } else if (!full) {
-        at = m0 + 27 + 3 * (r - POS_FULL_HALF);
+        at = m0 + 9 * (POS_FULL_HALF - 1) + 3 * (r - POS_FULL_HALF);
       } else {
-        at = m0 + 27 + 3 * (POS_ROUNDS - 2 * POS_FULL_HALF) + 9 * (r - (POS_ROUNDS - POS_FULL_HALF)) + 3 * q;
+        at = m0 + 9 * (POS_FULL_HALF - 1) + 3 * (POS_ROUNDS - 2 * POS_FULL_HALF) +
+             9 * (r - (POS_ROUNDS - POS_FULL_HALF)) + 3 * q;
       }
       if (st) {  // Montgomery form (k_wprog_canon_vars converts them at the end of the run), except
                  // the last round's x^5, which the next permutations' state combinations read
@@ -390,25 +419,50 @@ __device__ Fe pow_w3(const Fe& a, const uint64_t e[4]) {
   return started ? r : one<FrP>();
 }
 
-// One op of a level, on the quad of lanes (op_i, q).
-template <bool POS>
+// One op of a level, on the quad of lanes (op_i, q).  SEL: SELECT is compiled
+// in (false only in the general chain kernel, which sits at its register
+// cap).  LEAN: nothing but POS's Poseidon kind and SELECT is compiled in
+// (k_wprog_chain<true>, for runs of levels made of those two).
+template <int POS, bool SEL = true, bool LEAN = false>
 __device__ __forceinline__ void wprog_op(uint32_t op_i, uint32_t q, const uint4* __restrict__ ops,
                                          const uint2* __restrict__ terms, const uint32_t* __restrict__ coeff_m,
                                          const uint32_t* rc_s, const Fe* pc_s, uint32_t* __restrict__ z) {
   const uint4 op = ops[op_i];
   const int kind = op.x & 0xFF;
   const uint32_t alen = (op.x >> 8) & 0xFFF, blen = op.x >> 20, out = op.y;
-  if constexpr (POS) {
-    if (kind == WP_POSEIDON) {
+  if constexpr (POS != POS_NONE) {
+    if (kind == (POS == POS_RC ? WP_POSEIDON_RC : WP_POSEIDON)) {
       // lane q evaluates state combination q (stored contiguously at op.z)
       const uint32_t l2 = op.w & 0xFFFF;
       const uint32_t off = op.z + (q >= 1 ? alen : 0) + (q >= 2 ? blen : 0);
       const uint32_t len = q == 0 ? alen : q == 1 ? blen : q == 2 ? l2 : 0;
-      poseidon_quad(eval_lc(terms, off, len, coeff_m, z), q, out, op.w >> 16, pc_s, z);
+      const Fe in = eval_lc(terms, off, len, coeff_m, z);
+      if constexpr (POS == POS_RC)
+        poseidon_quad<true>(in, q, out, pos_rc_mask(op.w), pc_s, z, (int)pos_rc_half(op.w),
+                            (int)(2 * pos_rc_half(op.w) + pos_rc_partial(op.w)));
+      else
+        poseidon_quad<false>(in, q, out, op.w >> 16, pc_s, z, 0, 0);
       return;
     }
   }
-  const Fe a = eval_lc(terms, op.z, alen, coeff_m, z);
+  uint32_t aoff = op.z, al = alen;
+  if (SEL && kind == WP_SELECT) {
+    // c, t, f back to back at op.z (lengths a_len, b_len, op.w): lanes 0, 1, 2
+    // of the quad evaluate one each
+    aoff += (q >= 1 ? alen : 0) + (q >= 2 ? blen : 0);
+    al = q == 0 ? alen : q == 1 ? blen : q == 2 ? (op.w & 0xFFFF) : 0;
+  }
+  const Fe a = eval_lc(terms, aoff, al, coeff_m, z);
+  if (SEL && kind == WP_SELECT) {
+    const Fe t = quad_bcast<1>(a), f = quad_bcast<2>(a);
+    const Fe cr = reduce<FrP>(a);
+    uint32_t nz = 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) nz |= cr.v[i];
+    if (q == 0) st_canon(z, out, sel(nz != 0, t, f));  // lane 0 holds c
+    return;
+  }
+  if constexpr (LEAN) return;
   if (kind == WP_PERM) {
     const Fe r2 = fe_const<FrP>(FrP::R2);
     Fe x = mul<FrP>(a, r2);  // Montgomery form
@@ -467,20 +521,26 @@ __device__ __forceinline__ void wprog_op(uint32_t op_i, uint32_t q, const uint4*
   }
 }
 
-template <bool POS>
+// POS_RC: npc = the number of Poseidon constants of the program's round
+// counts (<= POS_RC_MAX_NCONST, checked by zkmi_wprog_create)
+template <int POS>
 __global__ void __launch_bounds__(256) k_wprog_level(const uint4* __restrict__ ops, uint32_t lo, uint32_t hi,
                                                      const uint2* __restrict__ terms,
                                                      const uint32_t* __restrict__ coeff_m,
                                                      const uint32_t* __restrict__ rc_m, uint32_t* __restrict__ z,
-                                                     size_t zstride) {
+                                                     size_t zstride, uint32_t npc) {
   z += blockIdx.y * zstride;  // batch blockIdx.y of a multi-batch run
   // Round constants in LDS: a global load inside the round loop would make
   // every round wait (vmcnt) for the previous round's stores to land.
   __shared__ uint32_t rc_s[MIMC_R * 8];
-  __shared__ Fe pc_s[POS ? POS_NCONST : 1];  // Poseidon constants, unpacked Montgomery
+  __shared__ Fe pc_s[POS == POS_RC ? POS_RC_MAX_NCONST : POS == POS_L2 ? POS_NCONST : 1];  // Poseidon constants,
+                                                                                          // unpacked Montgomery
   for (uint32_t i = threadIdx.x; i < MIMC_R * 8; i += blockDim.x) rc_s[i] = rc_m[i];
-  if constexpr (POS)
-    for (uint32_t i = threadIdx.x; i < POS_NCONST; i += blockDim.x) pc_s[i] = ld_canon(coeff_m, i);
+  if constexpr (POS != POS_NONE) {
+    const uint32_t n = POS == POS_RC ? (npc < (uint32_t)POS_RC_MAX_NCONST ? npc : (uint32_t)POS_RC_MAX_NCONST)
+                                     : (uint32_t)POS_NCONST;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) pc_s[i] = ld_canon(coeff_m, i);
+  }
   __syncthreads();
   // The program runs beside a proof whose MSM waves fill the same SIMDs:
   // top wave priority wins the VALU arbitration for this latency-critical
@@ -497,21 +557,33 @@ __global__ void __launch_bounds__(256) k_wprog_level(const uint4* __restrict__ o
 // launch: one 1024-thread workgroup per batch steps through the levels with a
 // barrier between them (global stores of a level are visible to the whole
 // workgroup after it), instead of one launch per level.
+// RC: the variant for runs of levels made of POSEIDON_RC and SELECT ops alone
+// (a Merkle path of ShieldedTransferCircuit is 32 x (two SELECTs, then one
+// permutation): levels of one to four ops): it holds the Poseidon constants
+// (npc of them) in LDS and compiles no other kind, so it fits the 128 VGPRs
+// that 1024 threads leave; the general variant keeps the registers it had.
+template <bool RC>
 __global__ void __launch_bounds__(1024) k_wprog_chain(const uint4* __restrict__ ops,
                                                       const uint32_t* __restrict__ level_start, uint32_t l0,
                                                       uint32_t l1, const uint2* __restrict__ terms,
                                                       const uint32_t* __restrict__ coeff_m,
                                                       const uint32_t* __restrict__ rc_m, uint32_t* __restrict__ z,
-                                                      size_t zstride) {
+                                                      size_t zstride, uint32_t npc) {
   z += blockIdx.y * zstride;
-  __shared__ uint32_t rc_s[MIMC_R * 8];
-  for (uint32_t i = threadIdx.x; i < MIMC_R * 8; i += blockDim.x) rc_s[i] = rc_m[i];
+  __shared__ uint32_t rc_s[RC ? 1 : MIMC_R * 8];
+  __shared__ Fe pc_s[RC ? POS_RC_MAX_NCONST : 1];
+  if constexpr (RC) {
+    const uint32_t n = npc < (uint32_t)POS_RC_MAX_NCONST ? npc : (uint32_t)POS_RC_MAX_NCONST;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) pc_s[i] = ld_canon(coeff_m, i);
+  } else {
+    for (uint32_t i = threadIdx.x; i < MIMC_R * 8; i += blockDim.x) rc_s[i] = rc_m[i];
+  }
   __builtin_amdgcn_s_setprio(3);
   for (uint32_t l = l0; l < l1; l++) {
     __syncthreads();
     const uint32_t lo = level_start[l], hi = level_start[l + 1];
     for (uint32_t op_i = lo + (threadIdx.x >> 2); op_i < hi; op_i += blockDim.x >> 2)
-      wprog_op<false>(op_i, threadIdx.x & 3, ops, terms, coeff_m, rc_s, nullptr, z);
+      wprog_op<RC ? POS_RC : POS_NONE, RC, RC>(op_i, threadIdx.x & 3, ops, terms, coeff_m, rc_s, pc_s, z);
   }
 }
 
@@ -574,6 +646,11 @@ struct zkmi_wprog {
   uint32_t num_perms = 0;
   std::vector<uint32_t> level_start;  // host: op ranges per level
   std::vector<uint32_t> op_kinds;     // host: kinds (level geometry)
+  // host, per level: LV_RC = holds POSEIDON_RC ops (k_wprog_level<POS_RC>), LV_SELECT = holds SELECT ops (not
+  // for the general chain kernel), LV_LEAN = POSEIDON_RC and SELECT ops alone (k_wprog_chain<true>)
+  std::vector<uint8_t> level_flags;
+  uint32_t rc_nconst = 0;  // Poseidon constants of the program's POSEIDON_RC round counts
+  bool rc_chain = true;    // runs of LV_LEAN levels go to k_wprog_chain<true>
   hipStream_t st = nullptr;           // the witness stream
   hipEvent_t done = nullptr, ctx_mark = nullptr;
   bool have_mark = false;
@@ -698,12 +775,28 @@ int zkmi_wprog_create(zkmi_ctx* ctx, const zkmi_wprog_desc* d, zkmi_wprog** out)
       return ZKMI_EINVAL;
     }
   std::vector<uint32_t> kinds(d->num_ops);
+  uint32_t rc_rounds_word = 0;  // R_f / 2 and R_p bits of the program's POSEIDON_RC ops (one setting per program:
+                                // the constants go to LDS once per launch)
+  bool have_l2_pos = false, have_rc = false;
   for (size_t i = 0; i < d->num_ops; i++) {
     const uint32_t* o = d->op + 4 * i;
     const uint32_t kind = o[0] & 0xFF, alen = (o[0] >> 8) & 0xFFF, blen = o[0] >> 20;
-    bool ok = kind >= WP_MUL && kind <= WP_INV1;
+    bool ok = kind >= WP_MUL && kind <= WP_SELECT;
     uint64_t span = 1;
-    if (kind == WP_POSEIDON) {
+    if (kind == WP_POSEIDON_RC) {
+      const uint32_t l2 = o[3] & 0xFFFF, half = pos_rc_half(o[3]), rounds = 2 * half + pos_rc_partial(o[3]);
+      ok = pos_rc_mask(o[3]) >= 1 && half >= 1 && rounds <= (uint32_t)POS_RC_MAX_ROUNDS &&
+           (uint64_t)o[2] + alen + blen + l2 <= d->num_terms && d->num_coeffs >= (size_t)3 * rounds + 9 &&
+           (!have_rc || (o[3] >> 19) == rc_rounds_word);
+      if (ok) {
+        span = pos_rc_trace_len(o[3]);
+        rc_rounds_word = o[3] >> 19;
+        have_rc = true;
+      }
+    } else if (kind == WP_SELECT) {
+      ok = (o[3] >> 16) == 0 && (uint64_t)o[2] + alen + blen + (o[3] & 0xFFFF) <= d->num_terms;
+    } else if (kind == WP_POSEIDON) {
+      have_l2_pos = true;
       const uint32_t l2 = o[3] & 0xFFFF, mask = o[3] >> 16;
       span = poseidon_trace_len(mask);
       ok = ok && kind != 0 && mask >= 1 && mask <= 7 && l2 < 4096 && (uint64_t)o[2] + alen + blen + l2 <= d->num_terms &&
@@ -718,6 +811,10 @@ int zkmi_wprog_create(zkmi_ctx* ctx, const zkmi_wprog_desc* d, zkmi_wprog** out)
       return ZKMI_EINVAL;
     }
     kinds[i] = kind;
+  }
+  if (have_l2_pos && have_rc) {  // the two constant tables start at the same coefficients
+    set_error("zkmi_wprog_create: POSEIDON and POSEIDON_RC ops in one program");
+    return ZKMI_EINVAL;
   }
   for (size_t i = 0; i < d->num_coeffs; i++) {
     const uint64_t* c = d->coeff + 4 * i;
@@ -743,6 +840,21 @@ int zkmi_wprog_create(zkmi_ctx* ctx, const zkmi_wprog_desc* d, zkmi_wprog** out)
   p->num_inputs = d->num_inputs;
   p->level_start.assign(d->level_start, d->level_start + d->num_levels + 1);
   p->op_kinds = kinds;
+  p->level_flags.assign(d->num_levels, 0);
+  for (size_t l = 0; l < d->num_levels; l++) {
+    uint8_t f = LV_LEAN;
+    for (uint32_t i = d->level_start[l]; i < d->level_start[l + 1]; i++) {
+      if (kinds[i] == WP_POSEIDON_RC) f |= LV_RC;
+      else if (kinds[i] == WP_SELECT) f |= LV_SELECT;
+      else f &= (uint8_t)~LV_LEAN;
+    }
+    p->level_flags[l] = f;
+  }
+  {  // measurement switch: per-level launches for every level with permutations, as without the variant
+    const char* e = getenv("ZKMI_DEBUG_WPROG_NO_RC_CHAIN");
+    p->rc_chain = !(e && e[0] == '1');
+  }
+  if (have_rc) p->rc_nconst = 3 * (2 * (rc_rounds_word >> 8) + (rc_rounds_word & 0xFF)) + 9;
   auto fail = [&](const char* what) {
     (void)hipGetLastError();
     set_error("zkmi_wprog_create: %s", what);
@@ -763,8 +875,10 @@ int zkmi_wprog_create(zkmi_ctx* ctx, const zkmi_wprog_desc* d, zkmi_wprog** out)
   {
     std::vector<uint8_t> is_raw(d->num_vars, 0);
     for (size_t i = 0; i < d->num_ops; i++) {
-      if (kinds[i] != WP_POSEIDON) continue;
-      const uint32_t out = d->op[4 * i + 1], len = poseidon_trace_len(d->op[4 * i + 3] >> 16);
+      if (kinds[i] != WP_POSEIDON && kinds[i] != WP_POSEIDON_RC) continue;
+      const uint32_t out = d->op[4 * i + 1], len = kinds[i] == WP_POSEIDON_RC
+                                                        ? pos_rc_trace_len(d->op[4 * i + 3])
+                                                        : poseidon_trace_len(d->op[4 * i + 3] >> 16);
       for (uint32_t k = 0; k < len; k++) {
         const bool final_x5 = k >= len - 9 && (k - (len - 9)) % 3 == 2;
         if (!final_x5) {
@@ -875,7 +989,13 @@ int zkmi_wprog_run_many(zkmi_ctx* ctx, zkmi_wprog* p, size_t nb, const uint64_t*
   // a 1024-thread workgroup
   auto chainable = [&](size_t l) {
     const uint32_t lo = p->level_start[l], hi = p->level_start[l + 1];
-    return hi > lo && hi - lo <= 256 && p->op_kinds[lo] != WP_PERM && p->op_kinds[lo] != WP_POSEIDON;
+    return hi > lo && hi - lo <= 256 && p->op_kinds[lo] != WP_PERM && p->op_kinds[lo] != WP_POSEIDON &&
+           !(p->level_flags[l] & (LV_RC | LV_SELECT));
+  };
+  // for k_wprog_chain<true>: POSEIDON_RC and SELECT ops alone
+  auto lean = [&](size_t l) {
+    const uint32_t lo = p->level_start[l], hi = p->level_start[l + 1];
+    return p->rc_chain && hi > lo && hi - lo <= 256 && (p->level_flags[l] & LV_LEAN);
   };
   for (size_t l = 0; l < nl;) {
     const uint32_t lo = p->level_start[l], hi = p->level_start[l + 1];
@@ -884,17 +1004,27 @@ int zkmi_wprog_run_many(zkmi_ctx* ctx, zkmi_wprog* p, size_t nb, const uint64_t*
       continue;
     }
     size_t l1 = l;
+    while (l1 < nl && lean(l1)) l1++;
+    if (l1 - l >= 2) {
+      k_wprog_chain<true><<<dim3(1, nby), 1024, 0, st>>>(p->d_ops, p->d_level_start, (uint32_t)l, (uint32_t)l1,
+                                                         p->d_terms, p->d_coeff, p->d_rc, z, zs, p->rc_nconst);
+      l = l1;
+      continue;
+    }
+    l1 = l;
     while (l1 < nl && chainable(l1)) l1++;
     if (l1 - l >= 2) {
-      k_wprog_chain<<<dim3(1, nby), 1024, 0, st>>>(p->d_ops, p->d_level_start, (uint32_t)l, (uint32_t)l1, p->d_terms,
-                                                   p->d_coeff, p->d_rc, z, zs);
+      k_wprog_chain<false><<<dim3(1, nby), 1024, 0, st>>>(p->d_ops, p->d_level_start, (uint32_t)l, (uint32_t)l1,
+                                                          p->d_terms, p->d_coeff, p->d_rc, z, zs, 0u);
       l = l1;
       continue;
     }
     const size_t threads = (size_t)(hi - lo) * 4;
-    auto kern = p->op_kinds[lo] == WP_POSEIDON ? k_wprog_level<true> : k_wprog_level<false>;
+    auto kern = (p->level_flags[l] & LV_RC)       ? k_wprog_level<POS_RC>
+                : p->op_kinds[lo] == WP_POSEIDON ? k_wprog_level<POS_L2>
+                                                 : k_wprog_level<POS_NONE>;
     kern<<<dim3((unsigned)((threads + 255) / 256), nby), 256, 0, st>>>(p->d_ops, lo, hi, p->d_terms, p->d_coeff,
-                                                                       p->d_rc, z, zs);
+                                                                       p->d_rc, z, zs, p->rc_nconst);
     l++;
   }
   if (p->num_perms) {

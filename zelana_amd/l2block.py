@@ -87,7 +87,10 @@ class GrainLFSR:
         out = []
         for _ in range(k):
             while True:
-                v = self._int_msb_first()
+                # F::from_random_bytes keeps the low MODULUS_BITS bits of the
+                # sample (ark-ff masks the rest off) before the range check: a
+                # no-op for prime_bits = 254, bit 254 dropped for 255
+                v = self._int_msb_first() & ((1 << MODULUS_BITS) - 1)
                 if v < R:
                     out.append(v)
                     break
@@ -100,13 +103,15 @@ class GrainLFSR:
 _PARAMS = {}
 
 
-def poseidon_params(rate=2, full_rounds=8, partial_rounds=56, alpha=5, skip_matrices=0):
+def poseidon_params(rate=2, full_rounds=8, partial_rounds=56, alpha=5, skip_matrices=0, prime_bits=MODULUS_BITS):
     """get_poseidon_config() (l2_circuit.rs:68-83): find_poseidon_ark_and_mds
-    (254, rate 2, 8 full, 56 partial, skip 0), capacity 1, alpha 5."""
-    key = (rate, full_rounds, partial_rounds, alpha, skip_matrices)
+    (254, rate 2, 8 full, 56 partial, skip 0), capacity 1, alpha 5.
+    prime_bits is find_poseidon_ark_and_mds' first argument (the Grain LFSR's
+    sample width; circuit/shielded.rs:366 passes 255)."""
+    key = (rate, full_rounds, partial_rounds, alpha, skip_matrices, prime_bits)
     if key not in _PARAMS:
         t = rate + 1
-        lfsr = GrainLFSR(MODULUS_BITS, t, full_rounds, partial_rounds)
+        lfsr = GrainLFSR(prime_bits, t, full_rounds, partial_rounds)
         ark = [lfsr.field_elements_rejection(t) for _ in range(full_rounds + partial_rounds)]
         for _ in range(skip_matrices):
             lfsr.field_elements_mod_p(2 * t)
@@ -230,6 +235,22 @@ class FpVar:
             res = res.square()
             if bit == "1":
                 res = res.mul(self)
+        return res
+
+    @staticmethod
+    def conditionally_select(cond: "Boolean", t: "FpVar", f: "FpVar") -> "FpVar":
+        """CondSelectGadget for FpVar (ark-r1cs-std 0.5 fields/fp/mod.rs): a
+        constant condition picks; two constants give the linear combination
+        cond t + (1 - cond) f; otherwise AllocatedFp::conditionally_select: the
+        result is a new witness with cond * (t - f) = result - f."""
+        cs = cond.cs
+        if cond.const:
+            return t if cond.v else f
+        if t.const and f.const:
+            return FpVar(cs, _lc_add(_lc_scale(cond.lc, t.v), _lc_scale(cond.negate().term(), f.v)),
+                         t.v if cond.v else f.v)
+        res = FpVar.witness(cs, t.v if cond.v else f.v)
+        cs.enforce(cond.lc, _lc_add(t.term(), f.term(), R - 1), _lc_add(res.lc, f.term(), R - 1))
         return res
 
     def enforce_equal(self, o):
