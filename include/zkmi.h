@@ -639,6 +639,56 @@ int zkmi_groth16_verify_each_encoded(zkmi_ctx* ctx, const zkmi_vk* vk, int fmt, 
                                      const uint64_t* inputs, uint8_t* valid, uint8_t* malformed,
                                      zkmi_verify_each_stats* stats);
 
+/* ----------------------------------- Poseidon hashing / note commitment tree
+ * The Poseidon sponge over Fr as a primitive (width 3: rate 2, capacity 1,
+ * x^5), one GPU lane per hash, and an append-only Merkle tree over it that
+ * lives in device memory.  Field elements are 4 x
+ * u64 little-endian.  Every INPUT may be any 256-bit value and is taken mod r
+ * (Fr::from_le_bytes_mod_order); every output is canonical.  All calls run on
+ * the context stream, return with their results on the host and open no
+ * stream (zkmi_ctx_stream_count is unchanged).  Destroy hashers and trees
+ * before their context, and a tree before its hasher. */
+typedef struct zkmi_poseidon zkmi_poseidon;     /* resident constants of one parameter set */
+/* consts: (3 (R_f + R_p) + 9) x 4 words in the order of a kind-9 op's table:
+ * ark[r][i] at 3 r + i, then mds[i][j].  ZKMI_EINVAL unless full_rounds is
+ * even and >= 2 and full_rounds + partial_rounds <= 72. */
+int zkmi_poseidon_create(zkmi_ctx* ctx, uint32_t full_rounds, uint32_t partial_rounds, const uint64_t* consts,
+                         zkmi_poseidon** out);
+void zkmi_poseidon_destroy(zkmi_poseidon* ph);
+/* out[i] = absorb(in[i * arity .. i * arity + arity)); squeeze one element.
+ * arity 1..4 (else ZKMI_EINVAL); in: n x arity x 4, out: n x 4 words, host
+ * pointers; n = 0 does nothing. */
+int zkmi_poseidon_hash_many(zkmi_ctx* ctx, const zkmi_poseidon* ph, size_t n, uint32_t arity, const uint64_t* in,
+                            uint64_t* out);
+
+/* The tree of the reference's MerkleTree: leaves at level 0, parent = H(left,
+ * right), a node with no leaf below it reads as e_level, where e_0 =
+ * empty_leaf and e_{l+1} = H(e_l, e_l); the root of an empty tree is e_depth.
+ * Level l stores ceil(capacity / 2^l) nodes of 32 bytes (64 MB for 2^20
+ * leaves).  depth 1..32, capacity 1..2^depth leaves, else ZKMI_EINVAL. */
+typedef struct zkmi_note_tree zkmi_note_tree;
+int zkmi_note_tree_create(zkmi_ctx* ctx, const zkmi_poseidon* ph, uint32_t depth, uint64_t capacity,
+                          const uint64_t empty_leaf[4], zkmi_note_tree** out);
+void zkmi_note_tree_destroy(zkmi_note_tree* t);
+int zkmi_note_tree_info(const zkmi_note_tree* t, uint64_t out[3]); /* depth, capacity, next_position */
+/* The n leaves go to positions [next, next + n) and every node above them is
+ * rehashed once.  *first (may be NULL) = the old next_position.  roots (may
+ * be NULL): n x 4 words, roots[k] = the root after leaf k alone of this call
+ * has been added to everything before it (what n single insertions would have
+ * returned one by one).  An append past the capacity is ZKMI_EINVAL and leaves
+ * the tree, its root and next_position as they were; n = 0 does nothing. */
+int zkmi_note_tree_append(zkmi_ctx* ctx, zkmi_note_tree* t, size_t n, const uint64_t* leaves, uint64_t* first,
+                          uint64_t* roots);
+int zkmi_note_tree_root(zkmi_ctx* ctx, const zkmi_note_tree* t, uint64_t out[4]);
+/* siblings: n x depth x 4 words, the leaf level first; the is-right bit of
+ * level l is bit l of the position.  A position >= next_position fails the
+ * whole call with ZKMI_EINVAL and nothing is written. */
+int zkmi_note_tree_paths(zkmi_ctx* ctx, const zkmi_note_tree* t, size_t n, const uint64_t* positions,
+                         uint64_t* siblings);
+/* out: the leaves [first, first + n) as stored (canonical); ZKMI_EINVAL when
+ * the range passes next_position */
+int zkmi_note_tree_leaves(zkmi_ctx* ctx, const zkmi_note_tree* t, uint64_t first, size_t n, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,15 +3,18 @@ batch-proof path.  The compute lives in libzkmi.so (HIP for
 gfx950, C ABI in include/zkmi.h); this package is the host-side mirror of the
 reference's BatchProver interface plus ctypes plumbing."""
 
-__all__ = ["ZkmiError", "ShieldedProver"]
+# names of zelana_amd/shielded.py handed out on first use
+_SHIELDED = ("ShieldedProver", "DeviceNoteTree", "shielded_hasher", "commit_many", "nullifier_many",
+             "derive_pk_many", "honest_many")
+__all__ = ["ZkmiError", *_SHIELDED]
 
 from ._lib import ZkmiError  # noqa: E402
 
 
 def __getattr__(name):
-    # ShieldedProver (zelana_amd/shielded.py) on first use: the package import
-    # stays as light as it was (no numpy-heavy module, no library load)
-    if name == "ShieldedProver":
-        from .shielded import ShieldedProver
-        return ShieldedProver
+    # on first use: the package import stays as light as it was (no
+    # numpy-heavy module, no library load)
+    if name in _SHIELDED:
+        from . import shielded
+        return getattr(shielded, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -165,6 +165,16 @@ SIGNATURES = [
                                                         ctypes.POINTER(VerifyStatsStruct)]),
     ("zkmi_groth16_verify_each_encoded", ctypes.c_int, [vp, vp, ctypes.c_int, sz, u8p, u64p, u8p, u8p,
                                                         ctypes.POINTER(VerifyStatsStruct)]),
+    ("zkmi_poseidon_create", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, u64p, ctypes.POINTER(vp)]),
+    ("zkmi_poseidon_destroy", None, [vp]),
+    ("zkmi_poseidon_hash_many", ctypes.c_int, [vp, vp, sz, ctypes.c_uint32, u64p, u64p]),
+    ("zkmi_note_tree_create", ctypes.c_int, [vp, vp, ctypes.c_uint32, ctypes.c_uint64, u64p, ctypes.POINTER(vp)]),
+    ("zkmi_note_tree_destroy", None, [vp]),
+    ("zkmi_note_tree_info", ctypes.c_int, [vp, u64p]),
+    ("zkmi_note_tree_append", ctypes.c_int, [vp, vp, sz, u64p, u64p, u64p]),
+    ("zkmi_note_tree_root", ctypes.c_int, [vp, vp, u64p]),
+    ("zkmi_note_tree_paths", ctypes.c_int, [vp, vp, sz, u64p, u64p]),
+    ("zkmi_note_tree_leaves", ctypes.c_int, [vp, vp, ctypes.c_uint64, sz, u64p]),
 ]
 
 

@@ -906,3 +906,113 @@ def groth16_prove_many(ctx: Context, pk: "ProvingKey", r1cs: R1CSDevice, dz: Dev
                        rs, ss):
     return groth16_prove_many_wait(groth16_prove_many_submit(ctx, pk, r1cs, dz, nb, stride, rs, ss))
 
+
+
+def _fe_words(vals, width: int = 1) -> np.ndarray:
+    """field elements for the C ABI: an (n, 4 * width) u64 array as it is, or
+    ints / 32-byte strings (any 256-bit value: the library takes them mod r)"""
+    if isinstance(vals, np.ndarray) and vals.dtype == np.uint64:
+        return np.ascontiguousarray(vals).reshape(-1, 4 * width)
+    raw = b"".join(int(v).to_bytes(32, "little") if isinstance(v, int) else bytes(v) for v in vals)
+    if len(raw) % (32 * width):
+        raise ValueError("field elements are 32 bytes each")
+    return np.frombuffer(raw, np.uint64).reshape(-1, 4 * width).copy()
+
+
+class PoseidonHasher:
+    """Resident constants of one Poseidon parameter set (zkmi_poseidon_create):
+    width 3, x^5, `params` as l2block.poseidon_params gives them."""
+
+    def __init__(self, ctx: Context, params):
+        if params["rate"] != 2 or params["capacity"] != 1 or params["alpha"] != 5:
+            raise ValueError("PoseidonHasher: rate 2, capacity 1, x^5 only")
+        self.ctx, self.params = ctx, params
+        self.h = vp()
+        ctx._track(self)
+        table = _fe_words([int(c) for row in params["ark"] for c in row] + [int(c) for row in params["mds"] for c in row])
+        check(lib().zkmi_poseidon_create(ctx.h, params["full"], params["partial"], _p64(table), ctypes.byref(self.h)),
+              "zkmi_poseidon_create")
+
+    def hash_many(self, tuples, arity: int | None = None) -> np.ndarray:
+        """zkmi_poseidon_hash_many: one sponge hash per tuple, as an (n, 4) u64
+        array.  tuples: an (n, 4 * arity) u64 array (arity given), or equally
+        long sequences of ints / 32-byte strings."""
+        if arity is None:
+            tuples = [tuple(t) for t in tuples]
+            arity = len(tuples[0]) if tuples else 1
+            if any(len(t) != arity for t in tuples):
+                raise ValueError("hash_many: tuples of one length")
+            tuples = [x for t in tuples for x in t]
+        ins = _fe_words(tuples, arity)
+        n = ins.shape[0]
+        out = np.zeros((max(n, 1), 4), np.uint64)
+        check(lib().zkmi_poseidon_hash_many(self.ctx.h, self.h, n, arity, _p64(ins), _p64(out)),
+              "zkmi_poseidon_hash_many")
+        return out[:n]
+
+    def close(self):
+        if self.h:
+            lib().zkmi_poseidon_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NoteTreeDevice:
+    """An append-only Merkle tree over a PoseidonHasher, resident in HBM
+    (zkmi_note_tree_create).  Arrays are (n, 4) u64 canonical words."""
+
+    def __init__(self, ctx: Context, hasher: PoseidonHasher, depth: int, capacity: int, empty_leaf):
+        self.ctx, self.hasher, self.depth, self.capacity = ctx, hasher, depth, capacity
+        self.h = vp()
+        ctx._track(self)
+        check(lib().zkmi_note_tree_create(ctx.h, hasher.h, depth, capacity, _p64(_fe_words([empty_leaf])),
+                                          ctypes.byref(self.h)), "zkmi_note_tree_create")
+
+    @property
+    def next_position(self) -> int:
+        info = np.zeros(3, np.uint64)
+        check(lib().zkmi_note_tree_info(self.h, _p64(info)), "zkmi_note_tree_info")
+        return int(info[2])
+
+    def append(self, leaves, want_roots: bool = True):
+        """-> (first position, (n, 4) per-insertion roots or None)"""
+        lv = _fe_words(leaves)
+        n = lv.shape[0]
+        first = ctypes.c_uint64(0)
+        roots = np.zeros((max(n, 1), 4), np.uint64) if want_roots else None
+        check(lib().zkmi_note_tree_append(self.ctx.h, self.h, n, _p64(lv), ctypes.byref(first),
+                                          None if roots is None else _p64(roots)), "zkmi_note_tree_append")
+        return int(first.value), None if roots is None else roots[:n]
+
+    def root(self) -> np.ndarray:
+        out = np.zeros(4, np.uint64)
+        check(lib().zkmi_note_tree_root(self.ctx.h, self.h, _p64(out)), "zkmi_note_tree_root")
+        return out
+
+    def paths(self, positions) -> np.ndarray:
+        """-> (n, depth, 4) siblings, the leaf level first"""
+        pos = np.ascontiguousarray(np.asarray(list(positions), np.uint64))
+        out = np.zeros((max(pos.size, 1), self.depth, 4), np.uint64)
+        check(lib().zkmi_note_tree_paths(self.ctx.h, self.h, pos.size, _p64(pos), _p64(out)), "zkmi_note_tree_paths")
+        return out[:pos.size]
+
+    def leaves(self, first: int, n: int) -> np.ndarray:
+        out = np.zeros((max(n, 1), 4), np.uint64)
+        check(lib().zkmi_note_tree_leaves(self.ctx.h, self.h, first, n, _p64(out)), "zkmi_note_tree_leaves")
+        return out[:n]
+
+    def close(self):
+        if self.h:
+            lib().zkmi_note_tree_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -179,6 +179,164 @@ class NoteTree:
         return notes
 
 
+# ================================================= batched hashes, device tree
+# The same hashes, domain constants and argument orders as above, n at a time
+# on the GPU (gpu.PoseidonHasher: one lane per hash), and the reference's
+# MerkleTree / RootHistory (sdk/privacy/src/merkle.rs) over a tree that lives in
+# HBM (gpu.NoteTreeDevice).  The functions above stay as they
+# are: they are what these are tested against.
+ROOT_HISTORY_SIZE = 100  # core/src/sequencer/storage/shielded_state.rs:24
+
+
+def shielded_hasher(ctx):
+    """A gpu.PoseidonHasher over shielded_params()."""
+    from . import gpu
+    return gpu.PoseidonHasher(ctx, shielded_params())
+
+
+def _hash_ints(h, tuples) -> list:
+    tuples = list(tuples)
+    if not tuples:
+        return []
+    return [_int4(row) for row in h.hash_many(tuples)]
+
+
+def commit_many(h, notes) -> list:
+    """note_commitment of every (value, randomness, owner_pk), one call."""
+    return _hash_ints(h, [(int(v) % R, _fr(rand), _fr(pk)) for v, rand, pk in notes])
+
+
+def nullifier_many(h, spending_keys, commitments, positions) -> list:
+    """nullifier(spending_key, commitment, position) element by element, one call."""
+    return _hash_ints(h, [(NULLIFIER_DOMAIN, _fr(sk), _fr(cm), int(pos) % R)
+                          for sk, cm, pos in zip(spending_keys, commitments, positions)])
+
+
+def derive_pk_many(h, keys) -> list:
+    """derive_pk of every spending key, one call."""
+    return _hash_ints(h, [(PK_DOMAIN, _fr(sk)) for sk in keys])
+
+
+def merkle_root_many(h, leaves, paths, bits_list) -> list:
+    """merkle_root of every (leaf, path, bits), one hash_many call per level."""
+    cur = [_fr(leaf) for leaf in leaves]
+    steps = [list(zip(p, b)) for p, b in zip(paths, bits_list)]
+    for level in range(max((len(s) for s in steps), default=0)):
+        live = [i for i, s in enumerate(steps) if level < len(s)]
+        pairs = []
+        for i in live:
+            sib, right = steps[i][level]
+            pairs.append((_fr(sib), cur[i]) if right else (cur[i], _fr(sib)))
+        for i, v in zip(live, _hash_ints(h, pairs)):
+            cur[i] = v
+    return cur
+
+
+class DeviceNoteTree:
+    """The note commitment tree resident on the GPU, with the reference's root
+    history.  empty_leaf=None is the reference's H(0) (a one-element absorb,
+    merkle.rs:126-134); empty_leaf=0 reproduces NoteTree.  Append-only: leaves
+    take the positions next_position, next_position + 1, ..."""
+
+    def __init__(self, ctx, depth: int = 32, capacity: int = 1 << 20, empty_leaf=None, hasher=None):
+        from collections import deque
+
+        from . import gpu
+        self.ctx, self.depth = ctx, depth
+        self.hasher = hasher or shielded_hasher(ctx)
+        if empty_leaf is None:
+            empty_leaf = _hash_ints(self.hasher, [(0,)])[0]
+        self.dev = gpu.NoteTreeDevice(ctx, self.hasher, depth, capacity, _fr(empty_leaf))
+        self.history = deque([self.root()], maxlen=ROOT_HISTORY_SIZE)  # newest last
+
+    @property
+    def next_position(self) -> int:
+        return self.dev.next_position
+
+    def append(self, leaves):
+        """-> (first position, the root after every single insertion as ints);
+        each of those roots enters the history, as n inserts would have put it."""
+        first, roots = self.dev.append([_fr(v) for v in leaves])
+        roots = [_int4(r) for r in roots]
+        self.history.extend(roots)
+        return first, roots
+
+    def root(self) -> int:
+        return _int4(self.dev.root())
+
+    def is_valid_root(self, root) -> bool:
+        """RootHistory::is_valid: the current root or one of the last ROOT_HISTORY_SIZE."""
+        return _fr(root) in self.history
+
+    def get(self, position: int) -> int:
+        return _int4(self.dev.leaves(position, 1)[0])
+
+    def paths(self, positions) -> list:
+        """[(sibling bytes per level, is-right bit per level)] as NoteTree.path."""
+        positions = [int(p) for p in positions]
+        sib = self.dev.paths(positions)
+        return [([row.tobytes() for row in sib[i]], [bool((p >> level) & 1) for level in range(self.depth)])
+                for i, p in enumerate(positions)]
+
+    def path(self, position: int):
+        return self.paths([position])[0]
+
+    def spend_notes(self, specs) -> list:
+        """NoteTree.spend_notes: specs are (value, randomness, spending_key,
+        position) per note; the positions must be the next free ones, in order."""
+        specs = list(specs)
+        first = self.next_position
+        if [int(s[3]) for s in specs] != list(range(first, first + len(specs))):
+            raise ValueError(f"spend_notes: an append-only tree takes positions {first}.. in order")
+        pks = [_b32(v) for v in derive_pk_many(self.hasher, [s[2] for s in specs])]
+        self.append(commit_many(self.hasher, [(v, rand, pk) for (v, rand, _, _), pk in zip(specs, pks)]))
+        notes = [InputNote(v, bytes(rand), pk, pos, bytes(sk)) for (v, rand, sk, pos), pk in zip(specs, pks)]
+        for n, (sibs, bits) in zip(notes, self.paths([n.position for n in notes])):
+            n.merkle_path, n.path_bits = sibs, bits
+        return notes
+
+    def close(self):
+        self.dev.close()
+
+
+def honest_many(h, inputs_list, outputs_list, fees=None, tree=None) -> list:
+    """The ShieldedTransfers that ShieldedTransfer.honest(inputs, outputs, fee)
+    builds, for many transfers: every nullifier and commitment from one batched
+    hash each; the root is `tree`'s when one is given, else the first input's
+    path folded on the device."""
+    inputs_list = [list(x) for x in inputs_list]
+    outputs_list = [list(x) for x in outputs_list]
+    fees = [None] * len(inputs_list) if fees is None else list(fees)
+    if not len(inputs_list) == len(outputs_list) == len(fees):
+        raise ValueError("honest_many: one input list, output list and fee per transfer")
+    flat_in = [n for ins in inputs_list for n in ins]
+    flat_out = [o for outs in outputs_list for o in outs]
+    cms = commit_many(h, [(n.value, n.randomness, n.owner_pk) for n in flat_in])
+    nfs = nullifier_many(h, [n.spending_key for n in flat_in], cms, [n.position for n in flat_in])
+    out_cms = commit_many(h, [(o.value, o.randomness, o.recipient_pk) for o in flat_out])
+    at, firsts = 0, []
+    for ins in inputs_list:
+        firsts.append(at if ins else None)
+        at += len(ins)
+    if tree is not None:
+        current = tree.root()
+        roots = [0 if k is None else current for k in firsts]
+    else:
+        have = [k for k in firsts if k is not None]
+        folded = iter(merkle_root_many(h, [cms[k] for k in have], [flat_in[k].merkle_path for k in have],
+                                       [flat_in[k].path_bits for k in have]))
+        roots = [0 if k is None else next(folded) for k in firsts]
+    res, ai, ao = [], 0, 0
+    for ins, outs, fee, root in zip(inputs_list, outputs_list, fees, roots):
+        if fee is None:
+            fee = sum(n.value for n in ins) - sum(o.value for o in outs)
+        res.append(ShieldedTransfer(_b32(root), [_b32(v) for v in nfs[ai:ai + len(ins)]],
+                                    [_b32(v) for v in out_cms[ao:ao + len(outs)]], int(fee), ins, outs))
+        ai += len(ins)
+        ao += len(outs)
+    return res
+
+
 # ================================================================ the circuit
 @dataclass
 class InputNote:  # shielded.rs:44-59 (InputNoteWitness)
