@@ -45,7 +45,8 @@ extern "C" {
 #define ZKMI_EINVAL (-1)   /* bad argument / malformed input */
 #define ZKMI_ENODEV (-2)   /* no usable GPU */
 #define ZKMI_EHIP (-3)     /* HIP runtime error */
-#define ZKMI_ENOMEM (-4)   /* device allocation failed */
+#define ZKMI_ENOMEM (-4)   /* device allocation failed, or a fixed-size device store could overflow
+                            * (zkmi_account_tree_apply past max_nodes) */
 #define ZKMI_EPOINT (-5)   /* point not on curve / not in subgroup */
 
 typedef struct zkmi_ctx zkmi_ctx;
@@ -688,6 +689,73 @@ int zkmi_note_tree_paths(zkmi_ctx* ctx, const zkmi_note_tree* t, size_t n, const
 /* out: the leaves [first, first + n) as stored (canonical); ZKMI_EINVAL when
  * the range passes next_position */
 int zkmi_note_tree_leaves(zkmi_ctx* ctx, const zkmi_note_tree* t, uint64_t first, size_t n, uint64_t* out);
+
+/* ------------------------------------------------ MiMC hashing / account tree
+ * The MiMC sponge of the zelana_batch circuit as a primitive (91 rounds of
+ * x <- (x + c_i)^7, c_i = (i+1)^3 + (i+1), key 0; hash_k(x_1..x_k) = the
+ * sponge over [k, x_1, .., x_k]), one GPU lane per hash, and the sparse
+ * account tree over it with batched ORDERED leaf writes (DESIGN.md section
+ * 2.12).  Field elements are 4 x u64 little-endian.  Every INPUT may be any
+ * 256-bit value and is taken mod r; every output is canonical.  All calls run
+ * on the context stream, return with their results on the host and open no
+ * stream (zkmi_ctx_stream_count is unchanged).  Destroy hashers and trees
+ * before their context, and a tree before its hasher. */
+typedef struct zkmi_mimc zkmi_mimc;             /* resident round constants and the four P(k) */
+int zkmi_mimc_create(zkmi_ctx* ctx, zkmi_mimc** out);
+void zkmi_mimc_destroy(zkmi_mimc* mh);
+/* out[i] = hash_arity(in[i * arity .. i * arity + arity)).  arity 1..4 (else
+ * ZKMI_EINVAL); in: n x arity x 4, out: n x 4 words, host pointers; n = 0
+ * does nothing. */
+int zkmi_mimc_hash_many(zkmi_ctx* ctx, const zkmi_mimc* mh, size_t n, uint32_t arity, const uint64_t* in,
+                        uint64_t* out);
+
+/* The tree of the reference's AccountTree: `depth` levels (1..32) over
+ * hash_2, a leaf at any position in [0, 2^depth), a node with no written leaf
+ * below it reads as e_level, where e_0 = 0 and e_{l+1} = hash_2(e_l, e_l); the
+ * root of an empty tree is e_depth.  Nodes live in an open-addressing table in
+ * device memory of max_nodes slots (8 + 32 bytes each), fixed at create: it
+ * neither grows nor rehashes.  The table may fill to its last slot, and the
+ * cost of that is the caller's: probing is linear, a lookup of an ABSENT node
+ * (most siblings of a depth-32 path) walks to the next empty slot, so about
+ * 1 / (1 - load)^2 / 2 slots on average and all max_nodes slots once the table
+ * is full; apply, paths and leaves then cost O(lookups x max_nodes).  Size
+ * max_nodes at twice the nodes expected (load <= 1/2: under 3 slots a lookup).
+ * depth outside 1..32 or max_nodes = 0 is ZKMI_EINVAL; ZKMI_ENOMEM when the
+ * table cannot be allocated. */
+typedef struct zkmi_account_tree zkmi_account_tree;
+int zkmi_account_tree_create(zkmi_ctx* ctx, const zkmi_mimc* mh, uint32_t depth, uint64_t max_nodes,
+                             zkmi_account_tree** out);
+void zkmi_account_tree_destroy(zkmi_account_tree* t);
+int zkmi_account_tree_info(const zkmi_account_tree* t, uint64_t out[3]); /* depth, max_nodes, nodes stored */
+/* n ordered leaf writes, leaves[k] to positions[k] for k = 0 .. n-1 in this
+ * order (a position may repeat), with what n single writes would have seen
+ * one by one.  Each output may be NULL:
+ *   siblings   n x depth x 4 words: the path of positions[k] as write k sees
+ *              it (after the writes before it), the leaf level first; the
+ *              is-right bit of level l is bit l of the position;
+ *   old_leaves n x 4 words: the leaf that write k replaces (0 when none);
+ *   roots      n x 4 words: the root after write k.
+ * n <= 65536 and every position < 2^depth, else ZKMI_EINVAL.  A call that
+ * could store more than max_nodes nodes, counted as nodes stored + n (depth +
+ * 1), is refused with ZKMI_ENOMEM before anything is launched.  A refused
+ * call (ZKMI_EINVAL, ZKMI_ENOMEM) leaves the tree, its root and its node count
+ * as they were.  The table is written by the call's last launch only, so a
+ * call that fails with ZKMI_EHIP before that launch does too; ZKMI_EHIP from
+ * the last launch on (a failed copy of the results) may leave the writes
+ * applied in the table while the outputs are incomplete: destroy such a tree.
+ * n = 0 does nothing. */
+int zkmi_account_tree_apply(zkmi_ctx* ctx, zkmi_account_tree* t, size_t n, const uint64_t* positions,
+                            const uint64_t* leaves, uint64_t* siblings, uint64_t* old_leaves, uint64_t* roots);
+int zkmi_account_tree_root(zkmi_ctx* ctx, const zkmi_account_tree* t, uint64_t out[4]);
+/* siblings: n x depth x 4 words against the current state, laid out as
+ * above; a position never written returns the e_l.  A position >= 2^depth
+ * fails the whole call with ZKMI_EINVAL and nothing is written. */
+int zkmi_account_tree_paths(zkmi_ctx* ctx, const zkmi_account_tree* t, size_t n, const uint64_t* positions,
+                            uint64_t* siblings);
+/* out: n x 4 words, the leaf at positions[i] (0 when never written); a
+ * position >= 2^depth is ZKMI_EINVAL with nothing written */
+int zkmi_account_tree_leaves(zkmi_ctx* ctx, const zkmi_account_tree* t, size_t n, const uint64_t* positions,
+                             uint64_t* out);
 
 #ifdef __cplusplus
 }

@@ -175,6 +175,16 @@ SIGNATURES = [
     ("zkmi_note_tree_root", ctypes.c_int, [vp, vp, u64p]),
     ("zkmi_note_tree_paths", ctypes.c_int, [vp, vp, sz, u64p, u64p]),
     ("zkmi_note_tree_leaves", ctypes.c_int, [vp, vp, ctypes.c_uint64, sz, u64p]),
+    ("zkmi_mimc_create", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
+    ("zkmi_mimc_destroy", None, [vp]),
+    ("zkmi_mimc_hash_many", ctypes.c_int, [vp, vp, sz, ctypes.c_uint32, u64p, u64p]),
+    ("zkmi_account_tree_create", ctypes.c_int, [vp, vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(vp)]),
+    ("zkmi_account_tree_destroy", None, [vp]),
+    ("zkmi_account_tree_info", ctypes.c_int, [vp, u64p]),
+    ("zkmi_account_tree_apply", ctypes.c_int, [vp, vp, sz, u64p, u64p, u64p, u64p, u64p]),
+    ("zkmi_account_tree_root", ctypes.c_int, [vp, vp, u64p]),
+    ("zkmi_account_tree_paths", ctypes.c_int, [vp, vp, sz, u64p, u64p]),
+    ("zkmi_account_tree_leaves", ctypes.c_int, [vp, vp, sz, u64p, u64p]),
 ]
 
 

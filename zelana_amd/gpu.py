@@ -1016,3 +1016,105 @@ class NoteTreeDevice:
             self.close()
         except Exception:
             pass
+
+
+class MimcHasher:
+    """Resident MiMC round constants (zkmi_mimc_create): the zelana_batch
+    circuit's hash_1 .. hash_4, one lane per hash."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.h = vp()
+        ctx._track(self)
+        check(lib().zkmi_mimc_create(ctx.h, ctypes.byref(self.h)), "zkmi_mimc_create")
+
+    def hash_many(self, tuples, arity: int | None = None) -> np.ndarray:
+        """zkmi_mimc_hash_many: hash_arity of every tuple, as an (n, 4) u64
+        array.  tuples: an (n, 4 * arity) u64 array (arity given), or equally
+        long sequences of ints / 32-byte strings."""
+        if arity is None:
+            tuples = [tuple(t) for t in tuples]
+            arity = len(tuples[0]) if tuples else 1
+            if any(len(t) != arity for t in tuples):
+                raise ValueError("hash_many: tuples of one length")
+            tuples = [x for t in tuples for x in t]
+        ins = _fe_words(tuples, arity)
+        n = ins.shape[0]
+        out = np.zeros((max(n, 1), 4), np.uint64)
+        check(lib().zkmi_mimc_hash_many(self.ctx.h, self.h, n, arity, _p64(ins), _p64(out)), "zkmi_mimc_hash_many")
+        return out[:n]
+
+    def close(self):
+        if self.h:
+            lib().zkmi_mimc_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AccountTreeDevice:
+    """The sparse MiMC account tree, resident in HBM (zkmi_account_tree_create):
+    any position below 2^depth, a node store of max_nodes slots.  Arrays are
+    (n, 4) u64 canonical words."""
+
+    def __init__(self, ctx: Context, hasher: MimcHasher, depth: int, max_nodes: int):
+        self.ctx, self.hasher, self.depth, self.max_nodes = ctx, hasher, depth, max_nodes
+        self.h = vp()
+        ctx._track(self)
+        check(lib().zkmi_account_tree_create(ctx.h, hasher.h, depth, max_nodes, ctypes.byref(self.h)),
+              "zkmi_account_tree_create")
+
+    @property
+    def node_count(self) -> int:
+        info = np.zeros(3, np.uint64)
+        check(lib().zkmi_account_tree_info(self.h, _p64(info)), "zkmi_account_tree_info")
+        return int(info[2])
+
+    def apply(self, positions, leaves):
+        """K ordered leaf writes -> ((K, depth, 4) siblings as write k sees
+        them, (K, 4) replaced leaves, (K, 4) roots after each write)"""
+        pos = np.ascontiguousarray(np.asarray(list(positions), np.uint64))
+        lv = _fe_words(leaves)
+        if lv.shape[0] != pos.size:
+            raise ValueError("apply: one leaf per position")
+        k = pos.size
+        sib = np.zeros((max(k, 1), self.depth, 4), np.uint64)
+        old, roots = np.zeros((max(k, 1), 4), np.uint64), np.zeros((max(k, 1), 4), np.uint64)
+        check(lib().zkmi_account_tree_apply(self.ctx.h, self.h, k, _p64(pos), _p64(lv), _p64(sib), _p64(old),
+                                            _p64(roots)), "zkmi_account_tree_apply")
+        return sib[:k], old[:k], roots[:k]
+
+    def root(self) -> np.ndarray:
+        out = np.zeros(4, np.uint64)
+        check(lib().zkmi_account_tree_root(self.ctx.h, self.h, _p64(out)), "zkmi_account_tree_root")
+        return out
+
+    def paths(self, positions) -> np.ndarray:
+        """-> (n, depth, 4) siblings against the current state, the leaf level first"""
+        pos = np.ascontiguousarray(np.asarray(list(positions), np.uint64))
+        out = np.zeros((max(pos.size, 1), self.depth, 4), np.uint64)
+        check(lib().zkmi_account_tree_paths(self.ctx.h, self.h, pos.size, _p64(pos), _p64(out)),
+              "zkmi_account_tree_paths")
+        return out[:pos.size]
+
+    def leaves(self, positions) -> np.ndarray:
+        pos = np.ascontiguousarray(np.asarray(list(positions), np.uint64))
+        out = np.zeros((max(pos.size, 1), 4), np.uint64)
+        check(lib().zkmi_account_tree_leaves(self.ctx.h, self.h, pos.size, _p64(pos), _p64(out)),
+              "zkmi_account_tree_leaves")
+        return out[:pos.size]
+
+    def close(self):
+        if self.h:
+            lib().zkmi_account_tree_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
