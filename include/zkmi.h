@@ -440,15 +440,21 @@ int zkmi_proof_serialize_compressed(const uint64_t a[8], const uint64_t b[16], c
  *         back at a_off, of lengths a_len, b_len and b_off & 0xFFFF (b_off's
  *         upper bits 0).
  *         Of a kind 7 / 9 trace only the last round's three x^5 may be read
- *         by other ops (the rest stays in Montgomery form until the run's
- *         last kernel).
+ *         by other ops, of a kind 4 trace only the permutation's output, the
+ *         last round's t^7 (the rest stays in Montgomery form until the run's
+ *         last kernels); zkmi_wprog_create refuses a term that reads another
+ *         trace value (ZKMI_EINVAL).
  *   term: 2 x u32 {z index, coefficient index}; <a,z> = sum over
  *         term[a_off .. a_off + a_len) of coeff * z
  *   levels: ops [level_start[l], level_start[l+1]) depend only on inputs and
- *         earlier levels.  A level is one launch, except runs of small levels
- *         (<= 256 ops each) without permutations, and runs of small levels
- *         made of kinds 9 and 10 alone, which one workgroup steps through
- *         in one launch (ZKMI_DEBUG_WPROG_NO_RC_CHAIN=1 in the environment
+ *         earlier levels.  A level may hold any mix of kinds in ANY order
+ *         (and may be empty): how it is launched is decided from all its ops,
+ *         so z is the same for every order; recorders put permutations first
+ *         only so that the quads of a wave share a kind.  A level is one
+ *         launch, except runs of small levels (<= 256 ops each) with no
+ *         permutation (kinds 4, 7, 9) or SELECT in them, and runs of small
+ *         levels made of kinds 9 and 10 alone, which one workgroup steps
+ *         through in one launch (ZKMI_DEBUG_WPROG_NO_RC_CHAIN=1 in the environment
  *         of zkmi_wprog_create turns the second kind of run off: a
  *         measurement switch). */
 typedef struct zkmi_wprog zkmi_wprog;

@@ -71,7 +71,7 @@ def test_program_levels_and_layout():
     _, _, prog = H.l2_record(inp, w)
     ls = prog.level_start
     assert ls[0] == 0 and ls[-1] == prog.op.shape[0] and (np.diff(ls.astype(np.int64)) > 0).all()
-    # permutations lead their level (the launch kind is read from its first op)
+    # permutations lead their level (the recorder's order: the quads of a wave share a kind)
     for lo, hi in zip(ls[:-1], ls[1:]):
         k = prog.kinds[lo:hi]
         npos = int((k == 7).sum())

@@ -83,7 +83,7 @@ __host__ __device__ constexpr uint32_t pos_rc_trace_len(uint32_t w) {
 }
 // which wprog_op variant a kernel instance holds: no Poseidon, kind 7, kind 9
 constexpr int POS_NONE = 0, POS_L2 = 1, POS_RC = 2;
-constexpr uint8_t LV_RC = 1, LV_SELECT = 2, LV_LEAN = 4;  // zkmi_wprog::level_flags
+constexpr uint8_t LV_RC = 1, LV_SELECT = 2, LV_LEAN = 4, LV_PERM = 8, LV_POS = 16;  // zkmi_wprog::level_flags
 
 // a * 2^-261 mod r for a < 2^261 with normalised limbs: Montgomery reduction
 // alone (a product with 1 without its 81 product mads)
@@ -645,9 +645,10 @@ struct zkmi_wprog {
   uint32_t num_raw = 0;
   uint32_t num_perms = 0;
   std::vector<uint32_t> level_start;  // host: op ranges per level
-  std::vector<uint32_t> op_kinds;     // host: kinds (level geometry)
-  // host, per level: LV_RC = holds POSEIDON_RC ops (k_wprog_level<POS_RC>), LV_SELECT = holds SELECT ops (not
-  // for the general chain kernel), LV_LEAN = POSEIDON_RC and SELECT ops alone (k_wprog_chain<true>)
+  // host, per level, from a scan of all its ops (a level may hold them in any order): LV_RC = holds POSEIDON_RC
+  // ops (k_wprog_level<POS_RC>), LV_POS = holds POSEIDON ops (k_wprog_level<POS_L2>), LV_PERM = holds PERM ops
+  // (a launch of its own), LV_SELECT = holds SELECT ops (not for the general chain kernel), LV_LEAN = POSEIDON_RC
+  // and SELECT ops alone (k_wprog_chain<true>)
   std::vector<uint8_t> level_flags;
   uint32_t rc_nconst = 0;  // Poseidon constants of the program's POSEIDON_RC round counts
   bool rc_chain = true;    // runs of LV_LEAN levels go to k_wprog_chain<true>
@@ -839,7 +840,6 @@ int zkmi_wprog_create(zkmi_ctx* ctx, const zkmi_wprog_desc* d, zkmi_wprog** out)
   p->num_vars = d->num_vars;
   p->num_inputs = d->num_inputs;
   p->level_start.assign(d->level_start, d->level_start + d->num_levels + 1);
-  p->op_kinds = kinds;
   p->level_flags.assign(d->num_levels, 0);
   for (size_t l = 0; l < d->num_levels; l++) {
     uint8_t f = LV_LEAN;
@@ -847,6 +847,8 @@ int zkmi_wprog_create(zkmi_ctx* ctx, const zkmi_wprog_desc* d, zkmi_wprog** out)
       if (kinds[i] == WP_POSEIDON_RC) f |= LV_RC;
       else if (kinds[i] == WP_SELECT) f |= LV_SELECT;
       else f &= (uint8_t)~LV_LEAN;
+      if (kinds[i] == WP_PERM) f |= LV_PERM;
+      else if (kinds[i] == WP_POSEIDON) f |= LV_POS;
     }
     p->level_flags[l] = f;
   }
@@ -870,11 +872,13 @@ int zkmi_wprog_create(zkmi_ctx* ctx, const zkmi_wprog_desc* d, zkmi_wprog** out)
   for (size_t i = 0; i < d->num_ops; i++)
     if (kinds[i] == WP_PERM) perm_out.push_back(d->op[4 * i + 1]);
   // Poseidon traces are stored in Montgomery form but for the last round's
-  // x^5 values; no op may read the others
+  // x^5 values, MiMC traces but for the permutation's output (k_wprog_canon
+  // converts those); no op may read the others
   std::vector<uint32_t> raw;
   {
     std::vector<uint8_t> is_raw(d->num_vars, 0);
     for (size_t i = 0; i < d->num_ops; i++) {
+      if (kinds[i] == WP_PERM) memset(is_raw.data() + d->op[4 * i + 1], 1, 4 * MIMC_R - 1);
       if (kinds[i] != WP_POSEIDON && kinds[i] != WP_POSEIDON_RC) continue;
       const uint32_t out = d->op[4 * i + 1], len = kinds[i] == WP_POSEIDON_RC
                                                         ? pos_rc_trace_len(d->op[4 * i + 3])
@@ -887,9 +891,10 @@ int zkmi_wprog_create(zkmi_ctx* ctx, const zkmi_wprog_desc* d, zkmi_wprog** out)
         }
       }
     }
-    for (size_t i = 0; i < d->num_terms && !raw.empty(); i++)
+    for (size_t i = 0; i < d->num_terms && !(raw.empty() && perm_out.empty()); i++)
       if (is_raw[d->term[2 * i]]) {
-        set_error("zkmi_wprog_create: term %zu reads a Poseidon trace value other than the output round's x^5", i);
+        set_error("zkmi_wprog_create: term %zu reads a trace value other than a permutation's output (MiMC: the last "
+                  "t^7; Poseidon: the output round's x^5)", i);
         wprog_free(p);
         return ZKMI_EINVAL;
       }
@@ -985,12 +990,12 @@ int zkmi_wprog_run_many(zkmi_ctx* ctx, zkmi_wprog* p, size_t nb, const uint64_t*
   k_wprog_inputs<<<dim3((unsigned)((p->num_inputs + 255) / 256), nby), 256, 0, st>>>(
       p->d_in, p->d_input_var, (uint32_t)p->num_inputs, z, zs);
   const size_t nl = p->level_start.size() - 1;
-  // chainable: no permutation (they sort first in their level), one pass of
-  // a 1024-thread workgroup
+  // chainable: no permutation anywhere in the level (the general chain kernel
+  // holds no Poseidon variant, and a permutation would hold up the run's one
+  // workgroup), one pass of a 1024-thread workgroup
   auto chainable = [&](size_t l) {
     const uint32_t lo = p->level_start[l], hi = p->level_start[l + 1];
-    return hi > lo && hi - lo <= 256 && p->op_kinds[lo] != WP_PERM && p->op_kinds[lo] != WP_POSEIDON &&
-           !(p->level_flags[l] & (LV_RC | LV_SELECT));
+    return hi > lo && hi - lo <= 256 && !(p->level_flags[l] & (LV_RC | LV_SELECT | LV_PERM | LV_POS));
   };
   // for k_wprog_chain<true>: POSEIDON_RC and SELECT ops alone
   auto lean = [&](size_t l) {
@@ -1020,9 +1025,9 @@ int zkmi_wprog_run_many(zkmi_ctx* ctx, zkmi_wprog* p, size_t nb, const uint64_t*
       continue;
     }
     const size_t threads = (size_t)(hi - lo) * 4;
-    auto kern = (p->level_flags[l] & LV_RC)       ? k_wprog_level<POS_RC>
-                : p->op_kinds[lo] == WP_POSEIDON ? k_wprog_level<POS_L2>
-                                                 : k_wprog_level<POS_NONE>;
+    auto kern = (p->level_flags[l] & LV_RC)    ? k_wprog_level<POS_RC>
+                : (p->level_flags[l] & LV_POS) ? k_wprog_level<POS_L2>
+                                               : k_wprog_level<POS_NONE>;
     kern<<<dim3((unsigned)((threads + 255) / 256), nby), 256, 0, st>>>(p->d_ops, lo, hi, p->d_terms, p->d_coeff,
                                                                        p->d_rc, z, zs, p->rc_nconst);
     l++;
