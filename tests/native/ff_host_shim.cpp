@@ -1,47 +1,52 @@
-// Host build of zelana_amd/csrc/ff.h (the exact source the gfx950 kernels use)
-// so the limb arithmetic can be unit-tested on CPU against Python integers.
-#include "../../zelana_amd/csrc/ff.h"
-using namespace zk;
-template <class P> static Fe ld(const uint32_t* w) { return unpack(w); }
-extern "C" {
-// op: 0 mul (Montgomery, raw), 1 sqr, 2 add, 3 sub, 4 reduce, 5 to_mont, 6 from_mont, 7 neg
-// field: 0 = Fq, 1 = Fr.  Inputs/outputs packed 8 x u32.
-void ff_op(int field, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, int n) {
+// Host build of zelana_amd/csrc/ff.h and ec.h (the exact source the gfx950
+// kernels use): the op table of tests/device/ff_ops.h looped over on the CPU,
+// so the limb arithmetic can be compared per op with Python integers
+// (tests/test_ff_ops_cpu.py) and with the device build of the same table
+// (tests/test_gpu_ff_ops.py).  Built into zelana_amd/libff_host.so.
+#include <string.h>
+
+#include "../device/ff_ops.h"
+
+using namespace ffops;
+
+template <class P>
+static void field_loop(int op, const uint32_t* in, uint32_t* out, uint32_t* flag, int n) {
   for (int i = 0; i < n; i++) {
-    Fe x = unpack(a + 8 * i), y = unpack(b + 8 * i), r;
-    if (field == 0) {
-      switch (op) {
-        case 0: r = mul<FqP>(x, y); break;
-        case 1: r = sqr<FqP>(x); break;
-        case 2: r = add<FqP>(x, y); break;
-        case 3: r = sub<FqP>(x, y); break;
-        case 4: r = reduce<FqP>(x); break;
-        case 5: r = to_mont<FqP>(x); break;
-        case 6: r = from_mont<FqP>(x); break;
-        default: r = neg<FqP>(x); break;
-      }
-    } else {
-      switch (op) {
-        case 0: r = mul<FrP>(x, y); break;
-        case 1: r = sqr<FrP>(x); break;
-        case 2: r = add<FrP>(x, y); break;
-        case 3: r = sub<FrP>(x, y); break;
-        case 4: r = reduce<FrP>(x); break;
-        case 5: r = to_mont<FrP>(x); break;
-        case 6: r = from_mont<FrP>(x); break;
-        default: r = neg<FrP>(x); break;
-      }
-    }
-    pack(out + 8 * i, r);
+    Fe a[N_IN], r[N_OUT];
+    memcpy(a, in + (size_t)i * N_IN * NL, sizeof a);
+    memcpy(r, out + (size_t)i * N_OUT * NL, sizeof r);
+    field_apply<P>(op, a, r, flag + i);
+    memcpy(out + (size_t)i * N_OUT * NL, r, sizeof r);
   }
 }
-// lazy-add then mul: (a + b) * c with limbwise add (exercises the 2^30-limb path)
-void ff_lazy_mul(int field, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out, int n) {
+template <class F>
+static void curve_loop(int op, const uint32_t* in, uint32_t* out, uint32_t* flag, int n) {
+  using T = typename F::T;
+  constexpr int W = sizeof(T) / sizeof(uint32_t);
+  static_assert(sizeof(T) == W * sizeof(uint32_t), "coordinates are plain limb arrays");
   for (int i = 0; i < n; i++) {
-    Fe s = add_lazy(unpack(a + 8 * i), unpack(b + 8 * i));
-    Fe s2 = add_lazy(unpack(c + 8 * i), unpack(c + 8 * i));
-    Fe r = field == 0 ? mul<FqP>(s, s2) : mul<FrP>(s, s2);
-    pack(out + 8 * i, r);
+    T a[N_IN], r[N_OUT];
+    memcpy(a, in + (size_t)i * N_IN * W, sizeof a);
+    curve_apply<F>(op, a, r, flag + i);
+    memcpy(out + (size_t)i * N_OUT * W, r, sizeof r);
+  }
+}
+
+extern "C" {
+// the signatures of ff_probe.hip's entries; 0, or -1 for an op the field does not have
+int ff_host_field(int field, int op, const uint32_t* in, uint32_t* out, uint32_t* flag, int n) {
+  switch (field) {
+    case 0: return field_op_supported<FqP>(op) ? (field_loop<FqP>(op, in, out, flag, n), 0) : -1;
+    case 1: return field_op_supported<FrP>(op) ? (field_loop<FrP>(op, in, out, flag, n), 0) : -1;
+    case 2: return field_op_supported<FqPn>(op) ? (field_loop<FqPn>(op, in, out, flag, n), 0) : -1;
+    default: return -1;
+  }
+}
+int ff_host_curve(int group, int op, const uint32_t* in, uint32_t* out, uint32_t* flag, int n) {
+  switch (group) {
+    case 0: return curve_op_supported<FqOps>(op) ? (curve_loop<FqOps>(op, in, out, flag, n), 0) : -1;
+    case 1: return curve_op_supported<Fq2Ops>(op) ? (curve_loop<Fq2Ops>(op, in, out, flag, n), 0) : -1;
+    default: return -1;
   }
 }
 }

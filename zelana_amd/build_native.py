@@ -20,6 +20,8 @@ HOST = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HERE, "libzelana_prover.so")   # C++ mirror of the reference prover, above the C ABI
 HOST_TEST = os.path.join(HERE, "test_batch_prover")    # its C++ unit tests (tests/host/test_batch_prover.cpp)
 SHARD_TEST = os.path.join(HERE, "test_sharded_msm")    # 2-rank sharded MSM over zkmi.h alone (tests/host/)
+FF_PROBE = os.path.join(HERE, "libzkmi_ffprobe.so")    # ff.h / ec.h op table on the device (tests/device/), tests only
+FF_HOST = os.path.join(HERE, "libff_host.so")          # the same table on the CPU (tests/native/ff_host_shim.cpp)
 ROCM_LIB = "/opt/rocm/lib"
 ARCH = os.environ.get("ZKMI_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -73,6 +75,7 @@ def build(verbose: bool = False) -> str:
         if r.returncode != 0:
             raise RuntimeError("link failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
     _build_host(verbose)
+    _build_ff_ops(verbose)
     if verbose:
         print("built", LIB)
     return LIB
@@ -96,6 +99,26 @@ def _build_host(verbose: bool):
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("host build failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
+        if verbose:
+            print("built", out)
+
+
+def _build_ff_ops(verbose: bool):
+    """The per-op test libraries over ff.h / ec.h alone (tests/device/ff_ops.h):
+    libzkmi_ffprobe.so (hipcc, device) and libff_host.so (g++, CPU).  Neither
+    links libzkmi.so, and only the tests load them."""
+    tests = os.path.join(HERE, "..", "tests")
+    table = os.path.join(tests, "device", "ff_ops.h")
+    hdrs = [table, os.path.join(CSRC, "ff.h"), os.path.join(CSRC, "ec.h")]
+    for out, src, cmd in ((FF_PROBE, os.path.join(tests, "device", "ff_probe.hip"),
+                           [HIPCC] + HIP_FLAGS + ["-shared", "-L" + ROCM_LIB, "-Wl,-rpath," + ROCM_LIB]),
+                          (FF_HOST, os.path.join(tests, "native", "ff_host_shim.cpp"), ["g++"] + CXX_FLAGS + ["-shared"])):
+        if os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in [src] + hdrs):
+            continue
+        cmd = cmd + ["-o", out, src]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("ff op table build failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
         if verbose:
             print("built", out)
 

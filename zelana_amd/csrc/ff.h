@@ -7,8 +7,11 @@
 //     headroom for 18 products per column (< 2^64) so no carry chains are needed
 //     inside a column (measured: v_mad_u64_u32 issues at the same rate as a
 //     plain VALU op on gfx950, see tools/mb_modmul.hip / profiles/).
-//   * Lazy reduction: mul accepts inputs < 8p with limbs < 1.5*2^30 and returns
-//     a value < 2p with normalised limbs (R > 32p), so no final subtraction.
+//   * Lazy reduction: mul accepts unreduced inputs (a*b < 169 p^2, R/p = 169.3)
+//     whose limbs are both < 2^30, or one factor's < 1.5*2^30 against a
+//     normalised one (see "lazy forms" below; with both factors at 1.5*2^30 a
+//     column of 8 products of 2.25*2^60 wraps 2^64), and returns a value < 2p
+//     with normalised limbs, so no final subtraction.
 //     add/sub return normalised values in [0, 2p).
 //   * Storage in HBM/LDS-less paths is the packed 8 x u32 (256-bit) form.
 // The GPU's Montgomery radix differs from arkworks' (2^256); conversion happens
@@ -425,7 +428,10 @@ ZK_HD Fe add_lazy(const Fe& a, const Fe& b) {
 // or both < 2^30 for a single product).
 //
 // a - b + K p in one signed-carry pass: normalised limbs, value a - b + Kp.
-// Caller guarantees 0 <= a - b + Kp < 2^261 (limbs of a, b may be up to 2^31).
+// Caller guarantees 0 <= a - b + Kp < 2^261.  Limbs of b may be up to 2^31;
+// limbs of a only up to 1.5 2^30 (a sum of three normalised limbs, ntt.hip):
+// a_i + (Kp)_i + carry is formed unsigned and read as int32, so it must stay
+// below 2^31 (with a's limbs at 2^31 the carry comes out 8 short).
 template <class P, int K>
 ZK_HD Fe subk(const Fe& a, const Fe& b) {
   static_assert(K == 2 || K == 4 || K == 6 || K == 8, "bias");
