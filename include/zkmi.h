@@ -763,6 +763,62 @@ int zkmi_account_tree_paths(zkmi_ctx* ctx, const zkmi_account_tree* t, size_t n,
 int zkmi_account_tree_leaves(zkmi_ctx* ctx, const zkmi_account_tree* t, size_t n, const uint64_t* positions,
                              uint64_t* out);
 
+/* -------------------------------------------------------------- nullifier set
+ * The spent-nullifier set of the shielded pool, resident in device memory,
+ * with an ORDERED batched spend.  A key is 32 raw
+ * bytes, compared bytewise: unlike every field-element input above it is NOT
+ * taken mod r (the reference keeps a HashSet<[u8; 32]>), so a caller whose
+ * keys are field elements must refuse non-canonical encodings itself
+ * (ShieldedPool.settle does).  The set holds an append-only log of its keys in
+ * insertion order (capacity x 32 bytes) and an open-addressing table of
+ * `slots` u32 entries, slots = the least power of two >= 2 capacity, fixed at
+ * create; nothing is ever removed.  All calls run on the context stream,
+ * return with their results on the host and open no stream.  Destroy a set
+ * before its context. */
+typedef struct zkmi_nullifier_set zkmi_nullifier_set;
+#define ZKMI_NF_ACCEPTED      0 /* every key of the transfer is now spent */
+#define ZKMI_NF_SKIPPED       1 /* eligible[t] = 0: the transfer took no part */
+#define ZKMI_NF_SPENT_STORED  2 /* detail = k: key k was in the set before the call */
+#define ZKMI_NF_SPENT_IN_CALL 3 /* detail = u: an accepted earlier transfer u of this call spent the key */
+#define ZKMI_NF_DUP_IN_TX     4 /* detail = k: key k equals an earlier key of the same transfer */
+/* capacity 0 or above 2^31 is ZKMI_EINVAL; ZKMI_ENOMEM when the log and the
+ * table cannot be allocated. */
+int zkmi_nullifier_set_create(zkmi_ctx* ctx, uint64_t capacity, zkmi_nullifier_set** out);
+void zkmi_nullifier_set_destroy(zkmi_nullifier_set* set);
+int zkmi_nullifier_set_info(const zkmi_nullifier_set* set, uint64_t out[3]); /* capacity, slots, keys stored */
+/* out[i] = 1 when keys[i] (n x 32 bytes, host) is stored, else 0.  n <= 2^24;
+ * n = 0 does nothing. */
+int zkmi_nullifier_set_contains(zkmi_ctx* ctx, const zkmi_nullifier_set* set, size_t n, const uint8_t* keys,
+                                uint8_t* out);
+/* ntx transfers of per_tx keys each (keys: ntx x per_tx x 32 bytes), with the
+ * result of taking them one by one, in order:
+ *   for t = 0 .. ntx-1:
+ *     eligible[t] = 0:                 (SKIPPED, 0); its keys enter nothing
+ *     else for k = 0 .. per_tx-1, the first k that fails decides:
+ *       key stored before this call:                         (SPENT_STORED, k)
+ *       key spent by an ACCEPTED earlier transfer u < t:     (SPENT_IN_CALL, u)
+ *       key equal to an earlier key of t:                    (DUP_IN_TX, k)
+ *     no k fails: (ACCEPTED, 0), and all keys of t are spent from here on.
+ * A refused transfer spends nothing, so a later transfer that shares a key
+ * with it alone is accepted.  verdict[t], detail[t]: ntx words each; eligible:
+ * ntx bytes, or NULL = all eligible; *rounds (may be NULL) = the parallel
+ * rounds the call took (0 when no eligible transfer reached them, 1 or 2 for
+ * honest input, the length of the longest chain of transfers each refused or
+ * accepted only through the one before it otherwise).  The accepted keys are
+ * appended to the log in transfer order, then key order.
+ * per_tx outside 1..4 or more than 2^24 keys in a call is ZKMI_EINVAL.  When
+ * the accepted keys do not fit the capacity the call returns ZKMI_ENOMEM
+ * before anything of the set is written: count, log and contains answers are
+ * as before, and verdict / detail are not written.  ZKMI_EHIP from the insert
+ * on may leave keys entered while the outputs are incomplete: destroy such a
+ * set.  ntx = 0 does nothing. */
+int zkmi_nullifier_set_spend(zkmi_ctx* ctx, zkmi_nullifier_set* set, size_t ntx, uint32_t per_tx, const uint8_t* keys,
+                             const uint8_t* eligible, uint32_t* verdict, uint32_t* detail, uint32_t* rounds);
+/* out: the keys [first, first + n) of the log, n x 32 bytes, in insertion
+ * order (what a restart feeds back through spend with per_tx = 1); ZKMI_EINVAL
+ * when the range passes the number of keys stored; n = 0 does nothing. */
+int zkmi_nullifier_set_log(zkmi_ctx* ctx, const zkmi_nullifier_set* set, uint64_t first, size_t n, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,10 +3,11 @@ batch-proof path.  The compute lives in libzkmi.so (HIP for
 gfx950, C ABI in include/zkmi.h); this package is the host-side mirror of the
 reference's BatchProver interface plus ctypes plumbing."""
 
-# names of zelana_amd/shielded.py handed out on first use
+# names of zelana_amd/shielded.py and shielded_pool.py handed out on first use
 _SHIELDED = ("ShieldedProver", "DeviceNoteTree", "shielded_hasher", "commit_many", "nullifier_many",
              "derive_pk_many", "honest_many")
-__all__ = ["ZkmiError", *_SHIELDED]
+_POOL = ("ShieldedPool",)
+__all__ = ["ZkmiError", *_SHIELDED, *_POOL]
 
 from ._lib import ZkmiError  # noqa: E402
 
@@ -17,4 +18,7 @@ def __getattr__(name):
     if name in _SHIELDED:
         from . import shielded
         return getattr(shielded, name)
+    if name in _POOL:
+        from . import shielded_pool
+        return getattr(shielded_pool, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

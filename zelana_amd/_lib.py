@@ -20,6 +20,7 @@ _lib = None
 vp = ctypes.c_void_p
 u64p = ctypes.POINTER(ctypes.c_uint64)
 u8p = ctypes.POINTER(ctypes.c_uint8)
+u32p = ctypes.POINTER(ctypes.c_uint32)
 sz = ctypes.c_size_t
 
 
@@ -185,6 +186,12 @@ SIGNATURES = [
     ("zkmi_account_tree_root", ctypes.c_int, [vp, vp, u64p]),
     ("zkmi_account_tree_paths", ctypes.c_int, [vp, vp, sz, u64p, u64p]),
     ("zkmi_account_tree_leaves", ctypes.c_int, [vp, vp, sz, u64p, u64p]),
+    ("zkmi_nullifier_set_create", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.POINTER(vp)]),
+    ("zkmi_nullifier_set_destroy", None, [vp]),
+    ("zkmi_nullifier_set_info", ctypes.c_int, [vp, u64p]),
+    ("zkmi_nullifier_set_contains", ctypes.c_int, [vp, vp, sz, u8p, u8p]),
+    ("zkmi_nullifier_set_spend", ctypes.c_int, [vp, vp, sz, ctypes.c_uint32, u8p, u8p, u32p, u32p, u32p]),
+    ("zkmi_nullifier_set_log", ctypes.c_int, [vp, vp, ctypes.c_uint64, sz, u8p]),
 ]
 
 

@@ -11,7 +11,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import ROW_NONE, R1CSStatusStruct, R1CSStruct, VerifyStatsStruct, ZkmiError, check, lib, u64p, u8p, vp
+from ._lib import (ROW_NONE, R1CSStatusStruct, R1CSStruct, VerifyStatsStruct, ZkmiError, check, lib, u32p, u64p, u8p,
+                   vp)
 
 
 def _p64(a: np.ndarray):
@@ -1111,6 +1112,98 @@ class AccountTreeDevice:
     def close(self):
         if self.h:
             lib().zkmi_account_tree_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _key_bytes(keys) -> np.ndarray:
+    """32-byte keys for the C ABI: an (n, 32) u8 array as it is, an (n, 4) u64
+    array, or a sequence of 32-byte strings / ints (little-endian, below
+    2^256).  Keys are raw bytes: nothing is reduced mod r."""
+    if isinstance(keys, np.ndarray) and keys.dtype == np.uint8:
+        return np.ascontiguousarray(keys).reshape(-1, 32)
+    if isinstance(keys, np.ndarray) and keys.dtype == np.uint64:
+        return np.ascontiguousarray(keys).reshape(-1, 4).view(np.uint8).reshape(-1, 32)
+    raw = b"".join(int(k).to_bytes(32, "little") if isinstance(k, int) else bytes(k) for k in keys)
+    if len(raw) % 32:
+        raise ValueError("keys are 32 bytes each")
+    return np.frombuffer(raw, np.uint8).reshape(-1, 32)
+
+
+NF_ACCEPTED, NF_SKIPPED, NF_SPENT_STORED, NF_SPENT_IN_CALL, NF_DUP_IN_TX = 0, 1, 2, 3, 4  # ZKMI_NF_*
+
+
+class NullifierSetDevice:
+    """The spent-nullifier set, resident in HBM (zkmi_nullifier_set_create): at
+    most `capacity` keys of 32 raw bytes, compared bytewise, kept in insertion
+    order."""
+
+    def __init__(self, ctx: Context, capacity: int):
+        self.ctx, self.capacity = ctx, capacity
+        self.h = vp()
+        ctx._track(self)
+        check(lib().zkmi_nullifier_set_create(ctx.h, capacity, ctypes.byref(self.h)), "zkmi_nullifier_set_create")
+
+    def info(self):
+        """(capacity, slots of the table, keys stored)"""
+        out = np.zeros(3, np.uint64)
+        check(lib().zkmi_nullifier_set_info(self.h, _p64(out)), "zkmi_nullifier_set_info")
+        return tuple(int(v) for v in out)
+
+    @property
+    def count(self) -> int:
+        return self.info()[2]
+
+    def contains(self, keys) -> list:
+        """[bool per key]"""
+        kb = _key_bytes(keys)
+        n = kb.shape[0]
+        out = np.zeros(max(n, 1), np.uint8)
+        check(lib().zkmi_nullifier_set_contains(self.ctx.h, self.h, n, kb.ctypes.data_as(u8p), out.ctypes.data_as(u8p)),
+              "zkmi_nullifier_set_contains")
+        return out[:n].astype(bool).tolist()
+
+    def spend(self, keys, per_tx: int, eligible=None):
+        """zkmi_nullifier_set_spend: len(keys) / per_tx transfers in order ->
+        ([verdict per transfer] (NF_*), [detail per transfer], rounds).
+        eligible: None = all, else one truth value per transfer."""
+        kb = _key_bytes(keys)
+        if per_tx < 1 or kb.shape[0] % per_tx:
+            raise ValueError("spend: per_tx keys per transfer")
+        ntx = kb.shape[0] // per_tx
+        el = None
+        if eligible is not None:
+            el = np.ascontiguousarray([1 if e else 0 for e in eligible], np.uint8)
+            if el.size != ntx:
+                raise ValueError("spend: one eligible flag per transfer")
+        verdict, detail = np.zeros(max(ntx, 1), np.uint32), np.zeros(max(ntx, 1), np.uint32)
+        rounds = ctypes.c_uint32(0)
+        check(lib().zkmi_nullifier_set_spend(self.ctx.h, self.h, ntx, per_tx, kb.ctypes.data_as(u8p),
+                                             None if el is None else el.ctypes.data_as(u8p),
+                                             verdict.ctypes.data_as(u32p), detail.ctypes.data_as(u32p),
+                                             ctypes.byref(rounds)), "zkmi_nullifier_set_spend")
+        return verdict[:ntx].tolist(), detail[:ntx].tolist(), int(rounds.value)
+
+    def load(self, keys):
+        """Restore from a persisted list (ShieldedState::load): spend with one
+        key per transfer and no mask, so duplicates collapse."""
+        return self.spend(keys, 1)
+
+    def log(self, first: int, n: int) -> list:
+        """the keys [first, first + n) in insertion order, as 32-byte strings"""
+        out = np.zeros((max(n, 1), 32), np.uint8)
+        check(lib().zkmi_nullifier_set_log(self.ctx.h, self.h, first, n, out.ctypes.data_as(u8p)),
+              "zkmi_nullifier_set_log")
+        return [out[i].tobytes() for i in range(n)]
+
+    def close(self):
+        if self.h:
+            lib().zkmi_nullifier_set_destroy(self.h)
             self.h = vp()
 
     def __del__(self):
