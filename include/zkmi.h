@@ -819,6 +819,84 @@ int zkmi_nullifier_set_spend(zkmi_ctx* ctx, zkmi_nullifier_set* set, size_t ntx,
  * when the range passes the number of keys stored; n = 0 does nothing. */
 int zkmi_nullifier_set_log(zkmi_ctx* ctx, const zkmi_nullifier_set* set, uint64_t first, size_t n, uint8_t* out);
 
+/* ------------------------------------------------------- encrypted-note store
+ * The encrypted notes of the shielded pool, resident in device memory beside
+ * their commitments and positions, and a batched scan that answers "which of
+ * these notes are mine" for up to 64 keys in one call (DESIGN.md section
+ * 2.14).  A note is what the reference's EncryptedNote holds: an ephemeral
+ * X25519 public key (32 bytes), a nonce (12 bytes) and a ChaCha20-Poly1305
+ * ciphertext with its 16-byte tag last, over value u64 | randomness 32 |
+ * memo_len u16 | memo.  The scan derives, per (key, note) pair, key =
+ * BLAKE3 derive_key("zelana-note-v1", X25519(decryption_key, ephemeral_pk) ||
+ * ephemeral_pk), checks the tag, decrypts, parses and confirms the commitment.
+ * X25519 is RFC 7748 with no contributory check: a low-order ephemeral_pk
+ * gives the all-zero shared secret and the scan carries on, as the
+ * reference's x25519-dalek does.  The store is append-only and fixed at
+ * create: headers in arrays of their own, ciphertexts at a fixed stride of
+ * max_ct rounded up to 16 bytes.  All calls run on the context stream, return
+ * with their results on the host and open no stream (zkmi_ctx_stream_count is
+ * unchanged).  Destroy a store before its context. */
+typedef struct zkmi_note_store zkmi_note_store;
+#define ZKMI_SCAN_NOT_MINE         0 /* the tag does not match, or the ciphertext is shorter than a tag */
+#define ZKMI_SCAN_MALFORMED        1 /* tag good; plaintext under 42 bytes or memo_len past its end */
+#define ZKMI_SCAN_WRONG_COMMITMENT 2 /* tag and parse good; the scheme's commitment differs from the stored one */
+#define ZKMI_SCAN_HIT              3
+#define ZKMI_COMMIT_NONE     0 /* no commitment check (the reference's decrypt_note) */
+#define ZKMI_COMMIT_MIMC     1 /* MiMC hash_3(owner_pk, value, randomness): the scan_notes handler */
+#define ZKMI_COMMIT_POSEIDON 2 /* the Poseidon sponge over (value, randomness, owner_pk): ShieldedPool's tree */
+/* capacity 1..2^26 notes; max_ct 58..65593: the longest ciphertext accepted,
+ * tag included (570 covers the reference's 512-byte memo cap).  Else
+ * ZKMI_EINVAL; ZKMI_ENOMEM when the arrays (capacity x (88 + max_ct rounded
+ * up to 16) bytes) cannot be allocated. */
+int zkmi_note_store_create(zkmi_ctx* ctx, uint64_t capacity, uint32_t max_ct, zkmi_note_store** out);
+void zkmi_note_store_destroy(zkmi_note_store* store);
+int zkmi_note_store_info(const zkmi_note_store* store, uint64_t out[4]); /* capacity, max_ct, notes stored, ciphertext bytes stored */
+/* n notes, appended in this order.  positions: n words, in any order, not
+ * contiguous; commitments, ephemeral_pks: n x 32 bytes; nonces: n x 12 bytes;
+ * ct_lens: n words, each 0..max_ct (a ciphertext too short to open is stored
+ * and scans as NOT_MINE); cts: the ciphertexts back to back.  ZKMI_EINVAL for
+ * a ct_len above max_ct or a position that repeats one of this call or one
+ * stored by an earlier call (a position names one leaf of the commitment
+ * tree: two notes there cannot both be right); ZKMI_ENOMEM when the notes do
+ * not fit the capacity.  A refused call writes nothing: info, get and scan
+ * answer as before.  n = 0 does nothing. */
+int zkmi_note_store_append(zkmi_ctx* ctx, zkmi_note_store* store, size_t n, const uint32_t* positions,
+                           const uint8_t* commitments, const uint8_t* ephemeral_pks, const uint8_t* nonces,
+                           const uint32_t* ct_lens, const uint8_t* cts);
+/* The notes [first, first + n) in append order, into the same arrays (what
+ * persistence and a restart need); each output may be NULL.  cts receives the
+ * ciphertexts back to back: n x max_ct bytes always suffice, and a first call
+ * for ct_lens alone gives the exact size.  ZKMI_EINVAL when the range passes
+ * the notes stored; n = 0 does nothing. */
+int zkmi_note_store_get(zkmi_ctx* ctx, const zkmi_note_store* store, uint64_t first, size_t n, uint32_t* positions,
+                        uint8_t* commitments, uint8_t* ephemeral_pks, uint8_t* nonces, uint32_t* ct_lens,
+                        uint8_t* cts);
+/* Scan every stored note at a position >= from_position with each of nkeys
+ * (decryption key, owner public key) pairs (nkeys x 32 bytes each; nkeys <= 64,
+ * 0 does nothing), one GPU lane per (key, note) pair.  scheme: ZKMI_COMMIT_*;
+ * mh may be NULL unless scheme is MIMC, ph unless it is POSEIDON, else
+ * ZKMI_EINVAL.  The commitment's inputs are taken mod r and its canonical
+ * little-endian bytes are compared with the stored 32 bytes.  Per key k:
+ *   stats[4 k + result]   the pairs of each ZKMI_SCAN_* result over all notes examined;
+ *   counts[k]             the hits returned, at most limit (1..65536);
+ *   slot k limit + j, j < counts[k], of positions (words), values (u64),
+ *   randomness and commitments (32 bytes), memo_lens (words) and memos
+ *   (max_ct - 58 bytes a slot; may be NULL): hit j of key k, in ASCENDING
+ *   POSITION order; the other slots are not written.  Bytes after a declared
+ *   memo are dropped, as the reference drops them;
+ *   scanned_to[k]         when more than limit hits exist: the position of the
+ *                         last hit returned, so a scan from scanned_to + 1
+ *                         loses nothing; otherwise the highest stored position
+ *                         >= from_position, or from_position when there is none.
+ * (The reference cuts its loop at limit in database-key order and sorts
+ * afterwards: a cut answer there is an arbitrary subset.)  The call keeps
+ * nkeys x notes x 37 bytes of workspace on the context. */
+int zkmi_note_scan(zkmi_ctx* ctx, const zkmi_note_store* store, const zkmi_mimc* mh, const zkmi_poseidon* ph,
+                   uint32_t scheme, size_t nkeys, const uint8_t* decryption_keys, const uint8_t* owner_pks,
+                   uint32_t from_position, uint32_t limit, uint32_t* counts, uint32_t* scanned_to, uint32_t* stats,
+                   uint32_t* positions, uint64_t* values, uint8_t* randomness, uint8_t* commitments,
+                   uint32_t* memo_lens, uint8_t* memos);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,13 @@ SIGNATURES = [
     ("zkmi_nullifier_set_contains", ctypes.c_int, [vp, vp, sz, u8p, u8p]),
     ("zkmi_nullifier_set_spend", ctypes.c_int, [vp, vp, sz, ctypes.c_uint32, u8p, u8p, u32p, u32p, u32p]),
     ("zkmi_nullifier_set_log", ctypes.c_int, [vp, vp, ctypes.c_uint64, sz, u8p]),
+    ("zkmi_note_store_create", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(vp)]),
+    ("zkmi_note_store_destroy", None, [vp]),
+    ("zkmi_note_store_info", ctypes.c_int, [vp, u64p]),
+    ("zkmi_note_store_append", ctypes.c_int, [vp, vp, sz, u32p, u8p, u8p, u8p, u32p, u8p]),
+    ("zkmi_note_store_get", ctypes.c_int, [vp, vp, ctypes.c_uint64, sz, u32p, u8p, u8p, u8p, u32p, u8p]),
+    ("zkmi_note_scan", ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint32, sz, u8p, u8p, ctypes.c_uint32, ctypes.c_uint32,
+                                      u32p, u32p, u32p, u32p, u64p, u8p, u8p, u32p, u8p]),
 ]
 
 

@@ -66,3 +66,35 @@ def blake3(data: bytes) -> bytes:
         lcv, rcv = merge(lo, lo + left, False), merge(lo + left, hi, False)
         return _compress(IV, lcv + rcv, 0, 64, PARENT | (ROOT if root else 0))[:8]
     return struct.pack("<8I", *merge(0, len(cvs), True))
+
+
+# ------------------------------------------------------------------ derive_key
+DERIVE_KEY_CONTEXT, DERIVE_KEY_MATERIAL = 1 << 5, 1 << 6
+
+
+def _hash_mode(data: bytes, key_words, mode: int) -> bytes:
+    """blake3() with a starting chaining value and a mode flag on every
+    compression; one chunk only (inputs of derive_key here are short)."""
+    if len(data) > 1024:
+        raise ValueError("derive_key: at most one chunk (1024 bytes) of context or material")
+    cv = list(key_words)
+    blocks = [data[i:i + 64] for i in range(0, max(len(data), 1), 64)] or [b""]
+    for i, b in enumerate(blocks):
+        flags = mode | (CHUNK_START if i == 0 else 0) | ((CHUNK_END | ROOT) if i == len(blocks) - 1 else 0)
+        cv = _compress(cv, _words(b), 0, len(b), flags)[:8]
+    return struct.pack("<8I", *cv)
+
+
+def derive_key_context(context: str | bytes) -> bytes:
+    """the context key of derive_key: the context string hashed from the IV
+    under DERIVE_KEY_CONTEXT (32 bytes, the chaining value the material starts from)"""
+    ctx = context.encode() if isinstance(context, str) else bytes(context)
+    return _hash_mode(ctx, IV, DERIVE_KEY_CONTEXT)
+
+
+def derive_key(context: str | bytes, material: bytes) -> bytes:
+    """blake3::Hasher::new_derive_key(context).update(material).finalize(),
+    32 bytes.  The two mode flags follow the published specification; no
+    independent vector pins them here."""
+    key = struct.unpack("<8I", derive_key_context(context))
+    return _hash_mode(bytes(material), key, DERIVE_KEY_MATERIAL)

@@ -22,6 +22,7 @@ HOST_TEST = os.path.join(HERE, "test_batch_prover")    # its C++ unit tests (tes
 SHARD_TEST = os.path.join(HERE, "test_sharded_msm")    # 2-rank sharded MSM over zkmi.h alone (tests/host/)
 FF_PROBE = os.path.join(HERE, "libzkmi_ffprobe.so")    # ff.h / ec.h op table on the device (tests/device/), tests only
 FF_HOST = os.path.join(HERE, "libff_host.so")          # the same table on the CPU (tests/native/ff_host_shim.cpp)
+NC_PROBE = os.path.join(HERE, "libzkmi_ncprobe.so")    # note_crypt.h op table on the device (tests/device/), tests only
 ROCM_LIB = "/opt/rocm/lib"
 ARCH = os.environ.get("ZKMI_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -76,6 +77,7 @@ def build(verbose: bool = False) -> str:
             raise RuntimeError("link failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
     _build_host(verbose)
     _build_ff_ops(verbose)
+    _build_nc_probe(verbose)
     if verbose:
         print("built", LIB)
     return LIB
@@ -121,6 +123,24 @@ def _build_ff_ops(verbose: bool):
             raise RuntimeError("ff op table build failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
         if verbose:
             print("built", out)
+
+
+def _build_nc_probe(verbose: bool):
+    """libzkmi_ncprobe.so: the op table over note_crypt.h alone
+    (tests/device/note_crypt_ops.h) on the device.  It does not link
+    libzkmi.so, and only the tests load it; the same table runs on the CPU as
+    a stand-alone program the tests build themselves (tests/host/note_crypt_check.cpp)."""
+    dev = os.path.join(HERE, "..", "tests", "device")
+    src = os.path.join(dev, "note_crypt_probe.hip")
+    deps = [src, os.path.join(dev, "note_crypt_ops.h"), os.path.join(CSRC, "note_crypt.h")]
+    if os.path.exists(NC_PROBE) and all(os.path.getmtime(d) <= os.path.getmtime(NC_PROBE) for d in deps):
+        return
+    cmd = [HIPCC] + HIP_FLAGS + ["-shared", "-L" + ROCM_LIB, "-Wl,-rpath," + ROCM_LIB, "-o", NC_PROBE, src]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("note_crypt probe build failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
+    if verbose:
+        print("built", NC_PROBE)
 
 
 if __name__ == "__main__":

@@ -326,6 +326,12 @@ static int account_tree_lookup(zkmi_ctx* ctx, const zkmi_account_tree* t, size_t
   return timer_flush(ctx);
 }
 
+// the hasher's resident table and context, for the other users of a zkmi_mimc (note_scan.hip)
+const Fe* mimc_device_table(const zkmi_mimc* mh, const zkmi_ctx** ctx) {
+  *ctx = mh->ctx;
+  return mh->d_table;
+}
+
 }  // namespace zk
 
 using namespace zk;

@@ -321,6 +321,13 @@ static int note_tree_append(zkmi_ctx* ctx, zkmi_note_tree* t, size_t n, const ui
   return 0;
 }
 
+// the hasher's resident table, rounds and context, for the other users of a zkmi_poseidon (note_scan.hip)
+const Fe* poseidon_device_table(const zkmi_poseidon* ph, uint32_t* half, uint32_t* rounds, uint32_t* nconst,
+                                const zkmi_ctx** ctx) {
+  *half = ph->half, *rounds = ph->rounds, *nconst = ph->nconst, *ctx = ph->ctx;
+  return ph->d_table;
+}
+
 }  // namespace zk
 
 using namespace zk;

@@ -1211,3 +1211,134 @@ class NullifierSetDevice:
             self.close()
         except Exception:
             pass
+
+
+SCAN_NOT_MINE, SCAN_MALFORMED, SCAN_WRONG_COMMITMENT, SCAN_HIT = 0, 1, 2, 3  # ZKMI_SCAN_*
+COMMIT_NONE, COMMIT_MIMC, COMMIT_POSEIDON = 0, 1, 2                         # ZKMI_COMMIT_*
+
+
+@dataclass
+class ScannedNote:
+    """One note found by a scan.  memo is the raw bytes the sender declared."""
+    position: int
+    commitment: bytes
+    value: int
+    randomness: bytes
+    memo: bytes
+
+
+class NoteStoreDevice:
+    """The encrypted notes of a pool, resident in HBM (zkmi_note_store_create):
+    at most `capacity` notes whose ciphertexts, tag included, are at most
+    max_ct bytes; append-only.  hashers: mimc= a MimcHasher for COMMIT_MIMC
+    scans, poseidon= a PoseidonHasher for COMMIT_POSEIDON ones."""
+
+    def __init__(self, ctx: Context, capacity: int, max_ct: int = 570, mimc=None, poseidon=None):
+        self.ctx, self.capacity, self.max_ct, self.mimc, self.poseidon = ctx, capacity, max_ct, mimc, poseidon
+        self.h = vp()
+        ctx._track(self)
+        check(lib().zkmi_note_store_create(ctx.h, capacity, max_ct, ctypes.byref(self.h)), "zkmi_note_store_create")
+
+    def info(self):
+        """(capacity, max_ct, notes stored, ciphertext bytes stored)"""
+        out = np.zeros(4, np.uint64)
+        check(lib().zkmi_note_store_info(self.h, _p64(out)), "zkmi_note_store_info")
+        return tuple(int(v) for v in out)
+
+    @property
+    def count(self) -> int:
+        return self.info()[2]
+
+    def append(self, notes):
+        """notes: [(position, commitment, ephemeral_pk, nonce, ciphertext)],
+        stored in this order.  Raises ZkmiError, with nothing stored, for a
+        ciphertext above max_ct, a repeated position or a full store."""
+        notes = list(notes)
+        n = len(notes)
+        if any(len(bytes(e)) != 32 or len(bytes(nc)) != 12 for _, _, e, nc, _ in notes):
+            raise ValueError("append: 32-byte ephemeral keys and 12-byte nonces")
+        pos = np.ascontiguousarray([p for p, *_ in notes], np.uint32).reshape(-1)
+        cm = _key_bytes([c for _, c, *_ in notes])
+        epk = np.frombuffer(b"".join(bytes(e) for _, _, e, _, _ in notes), np.uint8)
+        nonce = np.frombuffer(b"".join(bytes(nc) for _, _, _, nc, _ in notes), np.uint8)
+        lens = np.ascontiguousarray([len(ct) for *_, ct in notes], np.uint32).reshape(-1)
+        cts = np.frombuffer(b"".join(bytes(ct) for *_, ct in notes) or b"\0", np.uint8)
+        check(lib().zkmi_note_store_append(self.ctx.h, self.h, n, pos.ctypes.data_as(u32p), cm.ctypes.data_as(u8p),
+                                           epk.ctypes.data_as(u8p), nonce.ctypes.data_as(u8p),
+                                           lens.ctypes.data_as(u32p), cts.ctypes.data_as(u8p)),
+              "zkmi_note_store_append")
+
+    def append_arrays(self, positions, commitments, epks, nonces, ct_lens, cts):
+        """append() over ready arrays: u32 (n), u8 (n, 32), (n, 32), (n, 12), u32 (n), u8 (sum of ct_lens)"""
+        arr = [np.ascontiguousarray(a, t) for a, t in ((positions, np.uint32), (commitments, np.uint8), (epks, np.uint8),
+                                                       (nonces, np.uint8), (ct_lens, np.uint32), (cts, np.uint8))]
+        n = arr[0].size
+        if arr[1].size != 32 * n or arr[2].size != 32 * n or arr[3].size != 12 * n or arr[4].size != n or \
+                arr[5].size != int(arr[4].sum(dtype=np.uint64)):
+            raise ValueError("append_arrays: array sizes do not agree")
+        check(lib().zkmi_note_store_append(self.ctx.h, self.h, n, arr[0].ctypes.data_as(u32p), arr[1].ctypes.data_as(u8p),
+                                           arr[2].ctypes.data_as(u8p), arr[3].ctypes.data_as(u8p),
+                                           arr[4].ctypes.data_as(u32p), arr[5].ctypes.data_as(u8p)),
+              "zkmi_note_store_append")
+
+    def get(self, first: int = 0, n: int | None = None) -> list:
+        """the notes [first, first + n) in append order, as append() takes them"""
+        n = self.count - first if n is None else n
+        m = max(n, 1)
+        pos, lens = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        cm, epk, nonce = np.zeros((m, 32), np.uint8), np.zeros((m, 32), np.uint8), np.zeros((m, 12), np.uint8)
+        cts = np.zeros(m * self.max_ct, np.uint8)
+        check(lib().zkmi_note_store_get(self.ctx.h, self.h, first, n, pos.ctypes.data_as(u32p), cm.ctypes.data_as(u8p),
+                                        epk.ctypes.data_as(u8p), nonce.ctypes.data_as(u8p), lens.ctypes.data_as(u32p),
+                                        cts.ctypes.data_as(u8p)), "zkmi_note_store_get")
+        out, at = [], 0
+        for i in range(n):
+            out.append((int(pos[i]), cm[i].tobytes(), epk[i].tobytes(), nonce[i].tobytes(),
+                        cts[at:at + int(lens[i])].tobytes()))
+            at += int(lens[i])
+        return out
+
+    def scan(self, keys, owner_pks, scheme: int = COMMIT_POSEIDON, from_position: int = 0, limit: int = 1000,
+             memos: bool = True):
+        """zkmi_note_scan: every stored note at a position >= from_position
+        against every (keys[k], owner_pks[k]) -> per key ([ScannedNote] in
+        ascending position order, at most limit; scanned_to; [stats x 4]
+        indexed by SCAN_*)."""
+        kb, ob = _key_bytes(keys), _key_bytes(owner_pks)
+        nk = kb.shape[0]
+        if ob.shape[0] != nk:
+            raise ValueError("scan: one owner public key per decryption key")
+        if not 1 <= limit <= 65536:
+            raise ValueError("scan: limit 1..65536")
+        m, memo_cap = max(nk, 1), self.max_ct - 58
+        counts, to, stats = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros((m, 4), np.uint32)
+        pos, vals = np.zeros((m, limit), np.uint32), np.zeros((m, limit), np.uint64)
+        rand, cm = np.zeros((m, limit, 32), np.uint8), np.zeros((m, limit, 32), np.uint8)
+        mlen = np.zeros((m, limit), np.uint32)
+        memo = np.zeros((m, limit, max(memo_cap, 1)), np.uint8) if memos else None
+        kb, ob = np.ascontiguousarray(kb), np.ascontiguousarray(ob)
+        check(lib().zkmi_note_scan(self.ctx.h, self.h, self.mimc.h if self.mimc is not None else None,
+                                   self.poseidon.h if self.poseidon is not None else None, scheme, nk,
+                                   kb.ctypes.data_as(u8p), ob.ctypes.data_as(u8p), from_position, limit,
+                                   counts.ctypes.data_as(u32p), to.ctypes.data_as(u32p), stats.ctypes.data_as(u32p),
+                                   pos.ctypes.data_as(u32p), _p64(vals), rand.ctypes.data_as(u8p),
+                                   cm.ctypes.data_as(u8p), mlen.ctypes.data_as(u32p),
+                                   None if memo is None else memo.ctypes.data_as(u8p)), "zkmi_note_scan")
+        out = []
+        for k in range(nk):
+            hits = [ScannedNote(int(pos[k, j]), cm[k, j].tobytes(), int(vals[k, j]), rand[k, j].tobytes(),
+                                memo[k, j, :int(mlen[k, j])].tobytes() if memo is not None else b"")
+                    for j in range(int(counts[k]))]
+            out.append((hits, int(to[k]), [int(v) for v in stats[k]]))
+        return out
+
+    def close(self):
+        if self.h:
+            lib().zkmi_note_store_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

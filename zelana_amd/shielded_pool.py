@@ -8,7 +8,10 @@ tx_router.rs:219-346, storage/shielded_state.rs:89-175).  ShieldedPool holds
 that state on the GPU: the note commitment tree (shielded.DeviceNoteTree), the
 spent-nullifier set (gpu.NullifierSetDevice) and the resident
 verifying key; settle() turns wire-format proofs plus public inputs into
-per-transfer verdicts and updated pool state.
+per-transfer verdicts and updated pool state.  Given the transfers' encrypted
+output notes as well, settle() stores those of the accepted transfers beside
+their commitments (gpu.NoteStoreDevice) and scan() answers a
+wallet's "which notes are mine" in one call.
 
 Two rules of settle() differ from, or go beyond, a one-by-one replay of the
 reference; both are deliberate:
@@ -34,6 +37,7 @@ from .r1cs import R
 ACCEPTED, NONCANONICAL, BAD_ROOT, BAD_ENCODING, BAD_PROOF = "ACCEPTED", "NONCANONICAL", "BAD_ROOT", "BAD_ENCODING", \
     "BAD_PROOF"
 SPENT_STORED, SPENT_IN_CALL, DUP_IN_TX = "SPENT_STORED", "SPENT_IN_CALL", "DUP_IN_TX"
+NONE, MIMC, POSEIDON = 0, 1, 2  # commitment schemes of scan (gpu.COMMIT_*)
 
 
 @dataclass
@@ -75,7 +79,7 @@ class ShieldedPool:
 
     def __init__(self, ctx, prover_or_vk, depth: int = 32, capacity: int = 1 << 20,
                  nullifier_capacity: int = 1 << 20, empty_leaf=None, n_in: int | None = None,
-                 n_out: int | None = None):
+                 n_out: int | None = None, max_ct: int = 570):
         from . import gpu
         from .shielded import DeviceNoteTree
         self.ctx = ctx
@@ -98,9 +102,21 @@ class ShieldedPool:
         self.n_in, self.n_out = n_in, n_out
         self.tree = DeviceNoteTree(ctx, depth=depth, capacity=capacity, empty_leaf=empty_leaf)
         self.nullifiers = gpu.NullifierSetDevice(ctx, nullifier_capacity)
+        # the encrypted-note store: one note per leaf of the tree at most; made by the first call that needs it
+        self.max_ct, self._notes, self._mimc = max_ct, None, None
+
+    @property
+    def notes(self):
+        """the pool's gpu.NoteStoreDevice (capacity = the tree's, ciphertexts up to max_ct bytes)"""
+        if self._notes is None:
+            from . import gpu
+            self._mimc = gpu.MimcHasher(self.ctx)
+            self._notes = gpu.NoteStoreDevice(self.ctx, self.tree.dev.capacity, self.max_ct, mimc=self._mimc,
+                                              poseidon=self.tree.hasher)
+        return self._notes
 
     # ---------------------------------------------------------------- settle
-    def settle(self, fmt: int, raw_proofs, public_inputs, each: bool = False) -> list:
+    def settle(self, fmt: int, raw_proofs, public_inputs, each: bool = False, encrypted_notes=None) -> list:
         """One pile, in order -> [Settlement per transfer].  raw_proofs: the
         proofs as wire bytes of format fmt (gpu.PROOF_*), back to back or as a
         list; public_inputs: per transfer root, nullifiers, commitments, fee
@@ -116,7 +132,14 @@ class ShieldedPool:
         spends nothing); the commitments of the accepted transfers are
         appended in order by one append, and every new root enters the
         history.  Raises ZkmiError, with nothing changed, when the pile could
-        overflow the tree or the accepted nullifiers do not fit the set."""
+        overflow the tree or the accepted nullifiers do not fit the set.
+
+        encrypted_notes (optional): per transfer, one (ephemeral_pk, nonce,
+        ciphertext) per output commitment.  The notes of the ACCEPTED
+        transfers are stored at the positions their commitments received, in
+        the same call; a refused transfer stores nothing.  Their shapes are
+        checked before anything changes (ValueError).  Without the keyword no
+        note is stored and nothing else differs."""
         from . import gpu
         from ._lib import ZkmiError
         buf, nb = gpu._encoded(fmt, raw_proofs)
@@ -125,6 +148,13 @@ class ShieldedPool:
         width = 2 + self.n_in + self.n_out
         if len(public_inputs) != nb or any(len(x) != width for x in public_inputs):
             raise ValueError(f"{nb} proofs need {nb} x {width} public inputs")
+        if encrypted_notes is not None:
+            encrypted_notes = [[(bytes(e), bytes(nc), bytes(ct)) for e, nc, ct in x] for x in encrypted_notes]
+            if len(encrypted_notes) != nb or any(len(x) != self.n_out for x in encrypted_notes):
+                raise ValueError(f"{nb} transfers need {nb} x {self.n_out} encrypted notes")
+            if any(len(e) != 32 or len(nc) != 12 or len(ct) > self.max_ct for x in encrypted_notes for e, nc, ct in x):
+                raise ValueError(f"an encrypted note is a 32-byte key, a 12-byte nonce and at most {self.max_ct} "
+                                 "bytes of ciphertext")
         rows = [[_b32(v) for v in x] for x in public_inputs]  # 1. split: the 32-byte forms
         vals = [[int.from_bytes(b, "little") for b in row] for row in rows]
         status: list = [None] * nb
@@ -147,6 +177,9 @@ class ShieldedPool:
         if self.tree.next_position + sum(eligible) * self.n_out > self.tree.dev.capacity:
             raise ZkmiError(f"settle: {sum(eligible)} transfers of {self.n_out} commitments could pass the tree's "
                             f"capacity {self.tree.dev.capacity} from {self.tree.next_position}")
+        if encrypted_notes is not None and self.notes.count + sum(eligible) * self.n_out > self.notes.capacity:
+            raise ZkmiError(f"settle: {sum(eligible)} transfers of {self.n_out} notes could pass the note store's "
+                            f"capacity {self.notes.capacity} from {self.notes.count}")
         keys = [nf for row in rows for nf in row[1:1 + self.n_in]]  # 5. nullifiers
         verdicts, details, _ = self.nullifiers.spend(keys, self.n_in, eligible) if nb else ([], [], 0)
         names = {gpu.NF_SPENT_STORED: SPENT_STORED, gpu.NF_SPENT_IN_CALL: SPENT_IN_CALL, gpu.NF_DUP_IN_TX: DUP_IN_TX}
@@ -165,7 +198,31 @@ class ShieldedPool:
             for j, t in enumerate(accepted):
                 pos = list(range(first + j * self.n_out, first + (j + 1) * self.n_out))
                 out[t] = Settlement(ACCEPTED, None, pos, roots[(j + 1) * self.n_out - 1] if self.n_out else None)
+            if encrypted_notes is not None and leaves:  # 7. the notes, beside their commitments
+                self.notes.append([(out[t].positions[k], rows[t][1 + self.n_in + k]) + encrypted_notes[t][k]
+                                   for t in accepted for k in range(self.n_out)])
         return out
+
+    # ------------------------------------------------------------------ scan
+    def scan(self, decryption_key, owner_pk, from_position: int = 0, limit: int = 1000, scheme: int = POSEIDON):
+        """The stored notes at positions >= from_position that decryption_key
+        opens and whose commitment, recomputed under owner_pk by `scheme`
+        (POSEIDON: what this pool's tree holds; MIMC: the reference's
+        scan_notes handler; NONE: no check), equals the stored one ->
+        ([gpu.ScannedNote] in ascending position order, at most limit;
+        scanned_to; stats).  A memo comes back as str, or None when it is
+        empty or not UTF-8.  When more than limit notes match, scanned_to is
+        the position of the last one returned: continue from scanned_to + 1."""
+        if self._notes is None:
+            return [], from_position, [0, 0, 0, 0]
+        hits, scanned_to, stats = self.notes.scan([_b32(decryption_key)], [_b32(owner_pk)], scheme, from_position,
+                                                  limit)[0]
+        for h in hits:
+            try:
+                h.memo = h.memo.decode("utf-8") if h.memo else None
+            except UnicodeDecodeError:
+                h.memo = None
+        return hits, scanned_to, stats
 
     # ------------------------------------------------------------ delegates
     def nullifier_exists(self, nf) -> bool:
@@ -185,6 +242,9 @@ class ShieldedPool:
         return self.tree.paths(positions)
 
     def close(self):
+        if self._notes is not None:
+            self._notes.close()
+            self._mimc.close()
         self.nullifiers.close()
         self.tree.close()
         if self._own_vk:
