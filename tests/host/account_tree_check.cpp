@@ -86,7 +86,7 @@ static int apply(HostTree& t, const std::vector<uint32_t>& pos, const std::vecto
       old((size_t)K * 8, 0xA5A5A5A5u);
   for (uint32_t k = 0; k < K; k++) {
     const int32_t* pk = &pred[(size_t)k * (depth + 1)];
-    mimc_canon(&raw[(size_t)k * 8], &ver[(size_t)k * 8]);
+    fr_canon(&raw[(size_t)k * 8], &ver[(size_t)k * 8]);
     if (pk[0] < 0) memcpy(&old[(size_t)k * 8], at_node(t.keys.data(), t.vals.data(), t.slots, t.empty.data(), at_key(0, pos[k])), 32);
     for (uint32_t l = 0; l < depth; l++)
       if (pk[l + 1] < 0)

@@ -105,7 +105,7 @@ int main(int argc, char** argv) {
       t.capacity = cap;
       nt_geom(t.g, depth, cap);
       t.empty.resize((depth + 1) * 8);
-      posh_canon(leaf, t.empty.data());
+      fr_canon(leaf, t.empty.data());
       for (unsigned l = 0; l < depth; l++)
         posh_pair(&t.empty[8 * l], &t.empty[8 * l], &t.empty[8 * l + 8], pc.data(), half, rounds);
       // 0xA5 in every node never written: a read of one shows in the output
@@ -122,7 +122,7 @@ int main(int argc, char** argv) {
       for (uint64_t i = 0; i < n; i++) {
         uint32_t raw[8];
         CHECK(read_fe(fp, raw), "A: bad leaf");
-        posh_canon(raw, &t.nodes[(t.g.off[0] + first + i) * 8]);
+        fr_canon(raw, &t.nodes[(t.g.off[0] + first + i) * 8]);
       }
       for (uint32_t l = 1; l <= t.g.depth; l++) {
         uint64_t lo, cnt;

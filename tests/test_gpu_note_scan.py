@@ -267,6 +267,50 @@ def test_keys_in_one_call(full, pile):
     assert [(h.position, h.value) for h in bare[0]] == [(h[0], h[2]) for h in pile.expect(257, 0, 2)[0]]
 
 
+def test_block_offsets_with_a_run_of_two_blocks_a_lane(ctx, hashers):
+    """8,193 notes under 8 keys in one call are 33 x 8 = 264 blocks of 256
+    pairs, more than the one-workgroup prefix sum over the blocks' flag counts
+    has lanes (lane_util.h k_block_offsets<256>): a lane sums a run of two
+    blocks and the lanes behind lane 131 clamp to an empty run.  The notes are
+    random bytes but four real ones: store indices 0 and 256 (blocks 0 and 1
+    of the first key: the two blocks of lane 0's run) to the first key, 255 and
+    8,192 (blocks 231 and 263: the second block of another lane's run, and the
+    last block of all) to the last key.  The model classifies the four real
+    notes under every key and a sample of the others; the rest are NOT_MINE
+    under every key as the sample is: the model opens a note only when its 16
+    tag bytes match, which random bytes do with probability 2^-128."""
+    from zelana_amd import gpu
+    n, nk = 8193, 8
+    rng = random.Random(8193)
+    sks = [C.rnd(f"wide/sk/{k}") for k in range(nk)]
+    owners = [C.rnd(f"wide/owner/{k}") for k in range(nk)]
+    to = {0: 0, 255: nk - 1, 256: 0, n - 1: nk - 1}
+    notes = []
+    for i in range(n):
+        if i in to:
+            value, rand = 5000 + i, C.rnd(f"wide/rand/{i}")
+            epk, nonce, ct = NC.encrypt_note(value, rand, NC.public_key(sks[to[i]]), b"memo %d" % i,
+                                             esk=C.rnd(f"wide/esk/{i}"), nonce=C.rnd(f"wide/nonce/{i}", 12))
+            notes.append((i, _poseidon_commit(owners[to[i]], value, rand), epk, nonce, ct))
+        else:
+            notes.append((i, rng.randbytes(32), rng.randbytes(32), rng.randbytes(12), rng.randbytes(58 + i % 7)))
+    # the model: the real notes and a sample of the random ones under every key
+    want = []
+    for k in range(nk):
+        part = [notes[i] for i in sorted(to)] + [notes[1 + 1000 * k]]
+        hits, _, stats = NC.scan_model(part, sks[k], owners[k], _poseidon_commit)
+        stats[NC.NOT_MINE] += n - len(part)
+        want.append((hits, n - 1, stats))
+    assert [len(w[0]) for w in want] == [2] + [0] * (nk - 2) + [2]
+    assert all(w[2] == [n, 0, 0, 0] for w in want[1:-1]) and want[0][2] == want[-1][2] == [n - 2, 0, 0, 2]
+    s = gpu.NoteStoreDevice(ctx, n, 80, mimc=hashers[0], poseidon=hashers[1])
+    try:
+        s.append(notes)
+        assert [_flat(g) for g in s.scan(sks, owners, 2)] == want
+    finally:
+        s.close()
+
+
 def test_refusals_leave_the_store_as_it_was(ctx, hashers, pile):
     from zelana_amd import gpu
     s = gpu.NoteStoreDevice(ctx, 8, 100)

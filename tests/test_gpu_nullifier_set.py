@@ -210,6 +210,39 @@ def test_reason_follows_key_order_not_round_order(ctx):
             b.close()
 
 
+# ------------------------------------------- 2b. more blocks than the scan has lanes
+def test_block_offsets_with_a_run_of_two_blocks_a_lane(ctx):
+    """65,537 transfers are 257 blocks of 256, one more than the one-workgroup
+    prefix sum over the blocks' accepted counts has lanes (lane_util.h
+    k_block_offsets<256>): a lane sums a run of two blocks, lane 128 a run of
+    one, and the lanes behind it clamp to an empty run.  Transfers 255 / 256
+    (the last lane of block 0, the first of block 1) share a key, and so do 0 /
+    65,536 (the lone transfer of block 256): the later of each pair is refused
+    with the earlier as its detail, so blocks 1 and 256 count one less than
+    their lanes and every offset behind block 1 depends on it.  Verdicts,
+    details, count and the log's order against the sequential model."""
+    from zelana_amd import gpu
+    n = 256 * 256 + 1
+    keys = [M.key(i, b"wide") for i in range(n)]
+    keys[n - 1], keys[256] = keys[0], keys[255]
+    stored, order = set(), []
+    want_v, want_d = M.spend(stored, order, keys, 1)
+    assert (want_v[256], want_d[256]) == (M.SPENT_IN_CALL, 255)
+    assert (want_v[n - 1], want_d[n - 1]) == (M.SPENT_IN_CALL, 0)
+    assert want_v.count(M.ACCEPTED) == n - 2 == len(order)
+    s = gpu.NullifierSetDevice(ctx, 1 << 17)
+    try:
+        v, d, _ = s.spend(keys, 1)
+        bad = [t for t in range(n) if (v[t], d[t]) != (want_v[t], want_d[t])]
+        assert not bad, (bad[:5], [(v[t], d[t], want_v[t], want_d[t]) for t in bad[:5]])
+        assert s.count == len(order)
+        log = s.log(0, s.count)
+        bad = [i for i in range(len(order)) if log[i] != order[i]]
+        assert not bad, ("the log's order", bad[:5])
+    finally:
+        s.close()
+
+
 # ------------------------------------------------- 3. a small table, to the brim
 def test_capacity_16_wraps_shares_a_home_slot_and_refuses(ctx):
     b = Both(ctx, 16)

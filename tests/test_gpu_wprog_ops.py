@@ -263,7 +263,7 @@ def _root7(y):
     return pow(y, pow(7, -1, R - 1), R)  # x -> x^7 permutes Fr: 7 does not divide r - 1
 
 
-def _mimc_input_with_zero_round(k):
+def _perm_input_with_zero_round(k):
     """x whose round-k value t_k = t_{k-1}^7 + c_k is 0, solved backwards from round k"""
     t = 0
     for r in range(k, 0, -1):
@@ -273,7 +273,7 @@ def _mimc_input_with_zero_round(k):
 
 def test_perm_edges(ctx):
     rng = np.random.default_rng(7)
-    vals = [0, R - 1, R - 2, _mimc_input_with_zero_round(1), _mimc_input_with_zero_round(3), _rand(rng), _rand(rng)]
+    vals = [0, R - 1, R - 2, _perm_input_with_zero_round(1), _perm_input_with_zero_round(3), _rand(rng), _rand(rng)]
     # the model agrees that these inputs hit t_r = 0: t_r^2 = 0 in the trace
     for x, r in ((R - 2, 0), (vals[3], 1), (vals[4], 3)):
         p1 = M.build(2 + 364, [0, 1], [(PERM, 2, 0, [[(1, 1)]])])

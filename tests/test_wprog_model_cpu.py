@@ -130,10 +130,10 @@ def test_mimc_model_known_answer():
     p = M.build(2 + 364, [0, 1], [(M.PERM, 2, 0, [[(1, 1)]])])
     for x in (0, 1, M.R - 2, M.R - 1, 1 << 253):
         z = M.interpret(p, M.limbs([1, x]))
-        assert z[-1] == _mimc_out(x) and z[2] == pow(x + 2, 2, M.R)
+        assert z[-1] == _perm_out(x) and z[2] == pow(x + 2, 2, M.R)
 
 
-def _mimc_out(x):
+def _perm_out(x):
     for c in M.MIMC_C:
         x = pow((x + c) % M.R, 7, M.R)
     return x

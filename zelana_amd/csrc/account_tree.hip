@@ -8,17 +8,8 @@
 
 #include <vector>
 
-#include "mimc_hash.h"
-#include "zkmi_internal.h"
-
-struct zkmi_mimc {
-  zkmi_ctx* ctx = nullptr;
-  zk::Fe table[zk::MIMC_NTABLE];  // host copy (the empty-subtree chain is made on the host)
-  zk::Fe* d_table = nullptr;
-  ~zkmi_mimc() {
-    if (d_table) (void)hipFree(d_table);
-  }
-};
+#include "hashers.h"
+#include "lane_util.h"
 
 struct zkmi_account_tree {
   zkmi_ctx* ctx = nullptr;
@@ -48,17 +39,6 @@ constexpr uint32_t AT_ONE_WG = ATB;
 constexpr uint32_t AT_TILE = 1024;
 static unsigned at_blocks(uint64_t n) { return (unsigned)((n + ATB - 1) / ATB); }
 
-// the table into LDS: every lane of a wave reads the same constant at the same time
-__device__ __forceinline__ void mimc_table_lds(Fe* tab_s, const Fe* __restrict__ tab) {
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(tab);
-  uint32_t* dst = reinterpret_cast<uint32_t*>(tab_s);
-  for (uint32_t i = threadIdx.x; i < MIMC_NTABLE * NL; i += blockDim.x) dst[i] = src[i];
-  __syncthreads();
-}
-__device__ __forceinline__ void copy8(uint32_t* dst, const uint32_t* src) {
-#pragma unroll
-  for (int w = 0; w < 8; w++) dst[w] = src[w];
-}
 // node of level l above `pos` (level 32 of a depth-32 tree is the root, index 0)
 __device__ __forceinline__ uint64_t at_ancestor_key(uint32_t pos, uint32_t l) {
   return at_key(l, l >= 32 ? 0u : pos >> l);
@@ -68,7 +48,7 @@ __device__ __forceinline__ uint64_t at_ancestor_key(uint32_t pos, uint32_t l) {
 __global__ void __launch_bounds__(ATB) k_mimc_hash_many(const Fe* __restrict__ tab, const uint32_t* __restrict__ in,
                                                         uint32_t* __restrict__ out, size_t n, uint32_t arity) {
   __shared__ Fe tab_s[MIMC_NTABLE];
-  mimc_table_lds(tab_s, tab);
+  fe_table_lds(tab_s, tab, MIMC_NTABLE);
   const size_t i = blockIdx.x * (size_t)ATB + threadIdx.x;
   if (i >= n) return;
   mimc_hash(in + i * arity * 8, arity, out + i * 8, tab_s);
@@ -126,7 +106,7 @@ __global__ void __launch_bounds__(ATB) k_at_gather(const uint64_t* __restrict__ 
   if (t >= (uint64_t)K * (depth + 1)) return;
   const uint32_t k = (uint32_t)(t / (depth + 1)), s = (uint32_t)(t % (depth + 1));
   const uint32_t p = pos[k];
-  if (s == 0) mimc_canon(raw + (size_t)k * 8, ver + (size_t)k * 8);
+  if (s == 0) fr_canon(raw + (size_t)k * 8, ver + (size_t)k * 8);
   if (pred[t] >= 0) return;
   if (s == 0) copy8(old + (size_t)k * 8, at_node(keys, vals, slots, empty, at_key(0, p)));
   else copy8(sib + ((size_t)k * depth + (s - 1)) * 8, at_node(keys, vals, slots, empty, at_sibling_key(p, s - 1)));
@@ -152,7 +132,7 @@ __global__ void __launch_bounds__(ATB) k_at_level(const Fe* __restrict__ tab, co
                                                   const int32_t* __restrict__ pred, uint32_t* ver, uint32_t* sib,
                                                   uint32_t* old) {
   __shared__ Fe tab_s[MIMC_NTABLE];
-  mimc_table_lds(tab_s, tab);
+  fe_table_lds(tab_s, tab, MIMC_NTABLE);
   const uint32_t k = blockIdx.x * ATB + threadIdx.x;
   if (k >= K) return;
   at_level_lane(k, l, pos, K, depth, pred, ver, sib, old, tab_s);
@@ -163,7 +143,7 @@ __global__ void __launch_bounds__(ATB) k_at_levels(const Fe* __restrict__ tab, c
                                                    uint32_t K, uint32_t depth, const int32_t* __restrict__ pred,
                                                    uint32_t* ver, uint32_t* sib, uint32_t* old) {
   __shared__ Fe tab_s[MIMC_NTABLE];
-  mimc_table_lds(tab_s, tab);
+  fe_table_lds(tab_s, tab, MIMC_NTABLE);
   for (uint32_t l = 0; l < depth; l++) {
     if (threadIdx.x < K) at_level_lane(threadIdx.x, l, pos, K, depth, pred, ver, sib, old, tab_s);
     __syncthreads();
@@ -207,18 +187,10 @@ __global__ void __launch_bounds__(ATB) k_at_lookup(const uint64_t* __restrict__ 
 
 static int mimc_hash_many(zkmi_ctx* ctx, const zkmi_mimc* mh, size_t n, uint32_t arity, const uint64_t* in,
                           uint64_t* out) {
-  uint32_t *d_in, *d_out;
-  ZK_TRY(ctx->ws.get("mh_in", n * arity * 32, (void**)&d_in));
-  ZK_TRY(ctx->ws.get("mh_out", n * 32, (void**)&d_out));
-  ZK_HIP(hipMemcpyAsync(d_in, in, n * arity * 32, hipMemcpyHostToDevice, ctx->stream));
-  {
-    ScopedKernelTimer tm(ctx, "mimc_hash_many");
+  return hasher_hash_many(ctx, "mh_in", "mh_out", "mimc_hash_many", n, arity, in, out,
+                          [&](const uint32_t* d_in, uint32_t* d_out) {
     k_mimc_hash_many<<<at_blocks(n), ATB, 0, ctx->stream>>>(mh->d_table, d_in, d_out, n, arity);
-  }
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  ZK_HIP(hipStreamSynchronize(ctx->stream));
-  return timer_flush(ctx);
+  });
 }
 
 // positions already checked and narrowed; K in 1 .. AT_MAX_WRITES
@@ -326,12 +298,6 @@ static int account_tree_lookup(zkmi_ctx* ctx, const zkmi_account_tree* t, size_t
   return timer_flush(ctx);
 }
 
-// the hasher's resident table and context, for the other users of a zkmi_mimc (note_scan.hip)
-const Fe* mimc_device_table(const zkmi_mimc* mh, const zkmi_ctx** ctx) {
-  *ctx = mh->ctx;
-  return mh->d_table;
-}
-
 }  // namespace zk
 
 using namespace zk;
@@ -347,18 +313,10 @@ int zkmi_mimc_create(zkmi_ctx* ctx, zkmi_mimc** out) {
   zkmi_mimc* mh = new zkmi_mimc;
   mh->ctx = ctx;
   mimc_table(mh->table);
-  if (hipMalloc((void**)&mh->d_table, sizeof mh->table) != hipSuccess) {
-    (void)hipGetLastError();
+  const int rc = hasher_upload_table("zkmi_mimc_create", ctx, mh->table, MIMC_NTABLE, &mh->d_table);
+  if (rc != 0) {
     delete mh;
-    set_error("zkmi_mimc_create: hipMalloc failed");
-    return ZKMI_ENOMEM;
-  }
-  hipError_t e = hipMemcpyAsync(mh->d_table, mh->table, sizeof mh->table, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    delete mh;
-    set_error("zkmi_mimc_create: upload failed (%s)", hipGetErrorString(e));
-    return ZKMI_EHIP;
+    return rc;
   }
   *out = mh;
   return 0;
@@ -371,10 +329,7 @@ void zkmi_mimc_destroy(zkmi_mimc* mh) {
 
 int zkmi_mimc_hash_many(zkmi_ctx* ctx, const zkmi_mimc* mh, size_t n, uint32_t arity, const uint64_t* in,
                         uint64_t* out) {
-  if (!ctx || !mh || mh->ctx != ctx) {
-    set_error("zkmi_mimc_hash_many: null context or hasher, or a hasher of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_mimc_hash_many", "hasher", ctx, mh ? mh->ctx : nullptr)) return ZKMI_EINVAL;
   if (arity < 1 || arity > 4) {
     set_error("zkmi_mimc_hash_many: arity %u outside 1..4", arity);
     return ZKMI_EINVAL;
@@ -451,10 +406,7 @@ int zkmi_account_tree_info(const zkmi_account_tree* t, uint64_t out[3]) {
 
 int zkmi_account_tree_apply(zkmi_ctx* ctx, zkmi_account_tree* t, size_t n, const uint64_t* positions,
                             const uint64_t* leaves, uint64_t* siblings, uint64_t* old_leaves, uint64_t* roots) {
-  if (!ctx || !t || t->ctx != ctx) {
-    set_error("zkmi_account_tree_apply: null context or tree, or a tree of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_account_tree_apply", "tree", ctx, t ? t->ctx : nullptr)) return ZKMI_EINVAL;
   if (n > AT_MAX_WRITES) {
     set_error("zkmi_account_tree_apply: %zu writes in one call (at most %u)", n, AT_MAX_WRITES);
     return ZKMI_EINVAL;
@@ -492,10 +444,7 @@ int zkmi_account_tree_root(zkmi_ctx* ctx, const zkmi_account_tree* t, uint64_t o
 
 static int at_lookup_entry(const char* what, zkmi_ctx* ctx, const zkmi_account_tree* t, size_t n,
                            const uint64_t* positions, int mode, uint64_t* out) {
-  if (!ctx || !t || t->ctx != ctx) {
-    set_error("%s: null context or tree, or a tree of another context", what);
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned(what, "tree", ctx, t ? t->ctx : nullptr)) return ZKMI_EINVAL;
   if (n == 0) return 0;
   if (!positions || !out) {
     set_error("%s: null argument", what);

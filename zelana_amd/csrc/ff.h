@@ -96,6 +96,12 @@ struct FrP {
 struct FqPn : FqP {
   static constexpr bool ASM = false;
 };
+// The same for Fr: the compiler splits a column's chain of mads into parallel
+// partial sums, which costs adds and wins where a lone wave on a SIMD sees the
+// latency of every mad (the hashers' launches that do not fill the device)
+struct FrPn : FrP {
+  static constexpr bool ASM = false;
+};
 
 // ---------------------------------------------------------------- packing
 // 256-bit little-endian (8 x u32) <-> 9 x 29-bit limbs.
@@ -710,6 +716,27 @@ ZK_HD Fe pow(const Fe& a, const uint64_t e[4]) {
   }
   return r;
 }
+
+// ---------------------------------------------------------------- Fr words
+// An Fr element as 8 little-endian u32 words, the form in which the hashers
+// and the resident stores take and give field elements.
+// any 256-bit value -> Montgomery form of the value mod r (2^256 < 8r, what
+// the product accepts)
+ZK_HD Fe fr_in(const uint32_t* w) {
+  uint32_t x[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) x[i] = w[i];
+  return to_mont<FrP>(unpack(x));
+}
+// Montgomery form -> the canonical words (< r)
+ZK_HD void fr_out(uint32_t* w, const Fe& a) {
+  uint32_t x[8];
+  pack(x, from_mont<FrP>(a));
+#pragma unroll
+  for (int i = 0; i < 8; i++) w[i] = x[i];
+}
+// any 256-bit value -> the canonical words of the value mod r
+ZK_HD void fr_canon(const uint32_t* in, uint32_t* out) { fr_out(out, fr_in(in)); }
 
 // ---------------------------------------------------------------- Fq2
 // Fq2 = Fq[u]/(u^2 + 1)

@@ -24,36 +24,18 @@ constexpr int MIMC_ROUNDS = 91;
 // the table: c_0 .. c_90, then P(1) .. P(4); Montgomery form
 constexpr int MIMC_NTABLE = MIMC_ROUNDS + 4;
 
-// any 256-bit value -> Montgomery form of the value mod r (2^256 < 8r, what
-// ff.h's product accepts)
-ZK_HD Fe mimc_in(const uint32_t* w) {
-  uint32_t x[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) x[i] = w[i];
-  return to_mont<FrP>(unpack(x));
-}
-ZK_HD void mimc_out(uint32_t* w, const Fe& a) {
-  uint32_t x[8];
-  pack(x, from_mont<FrP>(a));
-#pragma unroll
-  for (int i = 0; i < 8; i++) w[i] = x[i];
-}
-ZK_HD void mimc_canon(const uint32_t* in, uint32_t* out) { mimc_out(out, mimc_in(in)); }
-
 // One round: t = x + c, t^7 = t^4 t^3.  t^3 = t^2 t and t^4 = t^2 t^2 do not
 // depend on each other: mul_x2 interleaves their two accumulator chains in one
 // instruction stream, so a round is three dependent products deep, not four.
-// Fr with compiler-scheduled products: the hashes of a level step are few, a
-// lone wave on a SIMD sees the latency of every mad of ff.h's one-chain form
-struct MimcP : FrP {
-  static constexpr bool ASM = false;
-};
+// The square and the last product are compiler-scheduled (ff.h's FrPn): the
+// hashes of a level step are few, a lone wave on a SIMD sees the latency of
+// every mad of the one-chain form
 ZK_HD Fe mimc_round(const Fe& x, const Fe& c) {
   const Fe t = add<FrP>(x, c);
-  const Fe t2 = sqr<MimcP>(t);
+  const Fe t2 = sqr<FrPn>(t);
   Fe t3, t4;
   mul_x2<FrP>(t2, t, t2, t2, t3, t4);
-  return mul<MimcP>(t4, t3);
+  return mul<FrPn>(t4, t3);
 }
 // P(x), x in Montgomery form, < 2r
 ZK_HD Fe mimc_permute(Fe x, const Fe* tab) {
@@ -66,24 +48,24 @@ ZK_HD void mimc_table(Fe* tab) {
   for (uint32_t i = 0; i < (uint32_t)MIMC_ROUNDS; i++) {
     const uint64_t c = (uint64_t)(i + 1) * (i + 1) * (i + 1) + (i + 1);
     uint32_t w[8] = {(uint32_t)c, (uint32_t)(c >> 32), 0, 0, 0, 0, 0, 0};
-    tab[i] = reduce<FrP>(mimc_in(w));
+    tab[i] = reduce<FrP>(fr_in(w));
   }
   for (uint32_t k = 1; k <= 4; k++) {
     uint32_t w[8] = {k, 0, 0, 0, 0, 0, 0, 0};
-    tab[MIMC_ROUNDS + k - 1] = reduce<FrP>(mimc_permute(mimc_in(w), tab));
+    tab[MIMC_ROUNDS + k - 1] = reduce<FrP>(mimc_permute(fr_in(w), tab));
   }
 }
 // hash_arity(in[0 .. arity)), arity 1..4; in: arity x 8 words
 ZK_HD void mimc_hash(const uint32_t* in, uint32_t arity, uint32_t* out, const Fe* tab) {
   Fe s = tab[MIMC_ROUNDS + arity - 1];
-  for (uint32_t i = 0; i < arity; i++) s = mimc_permute(add<FrP>(s, mimc_in(in + 8 * i)), tab);
-  mimc_out(out, s);
+  for (uint32_t i = 0; i < arity; i++) s = mimc_permute(add<FrP>(s, fr_in(in + 8 * i)), tab);
+  fr_out(out, s);
 }
 // hash_2(left, right): the tree's node hash
 ZK_HD void mimc_pair(const uint32_t* left, const uint32_t* right, uint32_t* out, const Fe* tab) {
-  Fe s = mimc_permute(add<FrP>(tab[MIMC_ROUNDS + 1], mimc_in(left)), tab);
-  s = mimc_permute(add<FrP>(s, mimc_in(right)), tab);
-  mimc_out(out, s);
+  Fe s = mimc_permute(add<FrP>(tab[MIMC_ROUNDS + 1], fr_in(left)), tab);
+  s = mimc_permute(add<FrP>(s, fr_in(right)), tab);
+  fr_out(out, s);
 }
 
 // ------------------------------------------------------- ordered leaf writes

@@ -11,17 +11,9 @@
 #include <unordered_set>
 #include <vector>
 
-#include "mimc_hash.h"
+#include "hashers.h"
+#include "lane_util.h"
 #include "note_crypt.h"
-#include "poseidon_hash.h"
-#include "zkmi_internal.h"
-
-namespace zk {
-// account_tree.hip / note_tree.hip: what a hasher keeps resident
-const Fe* mimc_device_table(const zkmi_mimc* mh, const zkmi_ctx** ctx);
-const Fe* poseidon_device_table(const zkmi_poseidon* ph, uint32_t* half, uint32_t* rounds, uint32_t* nconst,
-                                const zkmi_ctx** ctx);
-}  // namespace zk
 
 // Headers are arrays of their own (a wave reads 64 consecutive entries of
 // each); a ciphertext lies at index x stride, stride = max_ct rounded up to 16
@@ -67,9 +59,7 @@ __global__ void __launch_bounds__(NSC_ECDH) k_scan_ecdh(const uint32_t* __restri
   for (int w = 0; w < 8; w++) sc[w] = dkeys[8 * k + w], u[w] = epk[8 * (uint64_t)i + w];
   x25519(shared, sc, u);
   note_key(key, ctx_key.w, shared, u);
-  uint32_t* out = key_out + 8 * ((uint64_t)k * n + i);
-#pragma unroll
-  for (int w = 0; w < 8; w++) out[w] = key[w];
+  copy8(key_out + 8 * ((uint64_t)k * n + i), key);
 }
 
 // flag[k n + i] = the tag of note i matches under the pair's key;
@@ -84,8 +74,7 @@ __global__ void __launch_bounds__(NSC_B) k_scan_tag(const uint32_t* __restrict__
   bool ok = false;
   if (i < n && pos[i] >= from) {
     uint32_t key[8], nc[3];
-#pragma unroll
-    for (int w = 0; w < 8; w++) key[w] = keys[8 * ((uint64_t)k * n + i) + w];
+    copy8(key, keys + 8 * ((uint64_t)k * n + i));
 #pragma unroll
     for (int w = 0; w < 3; w++) nc[w] = nonce[4 * (uint64_t)i + w];
     ok = aead_tag_ok(key, nc, ct + (uint64_t)i * stride_words, len[i]);
@@ -95,51 +84,17 @@ __global__ void __launch_bounds__(NSC_B) k_scan_tag(const uint32_t* __restrict__
   if (threadIdx.x == 0) block_cnt[k * gridDim.x + blockIdx.x] = (uint32_t)c;
 }
 
-// block_cnt -> its exclusive prefix sums, in place; *total = their sum.  One
-// workgroup: a lane sums a run of blocks, the lanes' sums are scanned in LDS
-// (the shape of nullifier_set.hip's k_ns_scan).
-__global__ void __launch_bounds__(NSC_B) k_scan_offsets(uint32_t* block_cnt, uint32_t nblocks, uint32_t* total) {
-  __shared__ uint32_t sum_s[NSC_B];
-  const uint32_t per = (nblocks + NSC_B - 1) / NSC_B;
-  const uint32_t lo = threadIdx.x * per < nblocks ? threadIdx.x * per : nblocks;
-  const uint32_t hi = lo + per < nblocks ? lo + per : nblocks;
-  uint32_t s = 0;
-  for (uint32_t b = lo; b < hi; b++) s += block_cnt[b];
-  sum_s[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t run = 0;
-    for (int j = 0; j < NSC_B; j++) {
-      const uint32_t v = sum_s[j];
-      sum_s[j] = run;
-      run += v;
-    }
-    *total = run;
-  }
-  __syncthreads();
-  uint32_t run = sum_s[threadIdx.x];
-  for (uint32_t b = lo; b < hi; b++) {
-    const uint32_t v = block_cnt[b];
-    block_cnt[b] = run;
-    run += v;
-  }
-}
-
 // list[rank] = k n + i for every flagged pair, in key-major, append order
-// (the blocks and lanes of k_scan_tag)
+// (the blocks and lanes of k_scan_tag, block_cnt turned into offsets by
+// k_block_offsets)
 __global__ void __launch_bounds__(NSC_B) k_scan_compact(const uint8_t* __restrict__ flag, uint32_t n,
                                                         const uint32_t* __restrict__ block_off,
                                                         uint32_t* __restrict__ list) {
   __shared__ uint32_t wave_s[NSC_B / 64];
   const uint32_t i = blockIdx.x * NSC_B + threadIdx.x, k = blockIdx.y;
   const bool f = i < n && flag[(uint64_t)k * n + i];
-  const unsigned long long m = __ballot(f);
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wave_s[wave] = (uint32_t)__popcll(m);
-  __syncthreads();
+  const uint32_t rank = block_rank<NSC_B>(f, block_off + (k * gridDim.x + blockIdx.x), wave_s);
   if (!f) return;
-  uint32_t rank = block_off[k * gridDim.x + blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-  for (uint32_t w = 0; w < wave; w++) rank += wave_s[w];
   list[rank] = k * n + i;
 }
 
@@ -158,19 +113,12 @@ __global__ void __launch_bounds__(NSC_B) k_scan_open(const uint32_t* __restrict_
                                                      uint32_t half, uint32_t rounds, uint32_t nconst,
                                                      uint32_t* __restrict__ rec) {
   __shared__ Fe tab_s[SCHEME == 1 ? MIMC_NTABLE : SCHEME == 2 ? POSH_MAX_NCONST : 1];
-  if (SCHEME != 0) {
-    const uint32_t words = (SCHEME == 1 ? (uint32_t)MIMC_NTABLE : nconst) * NL;
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(table);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(tab_s);
-    for (uint32_t j = threadIdx.x; j < words; j += NSC_B) dst[j] = src[j];
-    __syncthreads();
-  }
+  if (SCHEME != 0) fe_table_lds(tab_s, table, SCHEME == 1 ? (uint32_t)MIMC_NTABLE : nconst);
   const uint32_t j = blockIdx.x * NSC_B + threadIdx.x;
   if (j >= nflag) return;
   const uint32_t pair = list[j], k = pair / n, i = pair % n;
   uint32_t key[8], nc[3], pt[16];
-#pragma unroll
-  for (int w = 0; w < 8; w++) key[w] = keys[8 * (uint64_t)pair + w];
+  copy8(key, keys + 8 * (uint64_t)pair);
 #pragma unroll
   for (int w = 0; w < 3; w++) nc[w] = nonce[4 * (uint64_t)i + w];
   const uint32_t body = len[i] - AEAD_TAG;  // flagged: len >= 16
@@ -198,8 +146,7 @@ __global__ void __launch_bounds__(NSC_B) k_scan_open(const uint32_t* __restrict_
   }
   uint32_t* r = rec + (uint64_t)j * NSC_REC_WORDS;
   r[0] = result, r[1] = pos[i], r[2] = h.value[0], r[3] = h.value[1];
-#pragma unroll
-  for (int w = 0; w < 8; w++) r[4 + w] = h.randomness[w];
+  copy8(r + 4, h.randomness);
   r[12] = h.memo_len, r[13] = pair, r[14] = 0, r[15] = 0;
 }
 
@@ -216,8 +163,7 @@ __global__ void __launch_bounds__(NSC_B) k_scan_memo(const uint32_t* __restrict_
   const uint32_t pair = sel[2 * j], memo_len = sel[2 * j + 1], i = pair % n;
   if (note_memo_words(memo_len) > memo_words) return;  // cannot happen: memo_len <= body - 42 <= max_ct - 58
   uint32_t key[8], nc[3];
-#pragma unroll
-  for (int w = 0; w < 8; w++) key[w] = keys[8 * (uint64_t)pair + w];
+  copy8(key, keys + 8 * (uint64_t)pair);
 #pragma unroll
   for (int w = 0; w < 3; w++) nc[w] = nonce[4 * (uint64_t)i + w];
   note_memo(memo_out + (uint64_t)j * memo_words, key, nc, ct + (uint64_t)i * stride_words, len[i] - AEAD_TAG,
@@ -276,7 +222,7 @@ static int note_scan(zkmi_ctx* ctx, const zkmi_note_store* s, const Fe* table, u
   ZK_HIP(hipGetLastError());
   {
     ScopedKernelTimer tm(ctx, "note_scan_compact");
-    k_scan_offsets<<<1, NSC_B, 0, ctx->stream>>>(d_block, nblocks, d_total);
+    k_block_offsets<NSC_B><<<1, NSC_B, 0, ctx->stream>>>(d_block, nblocks, d_total);
     k_scan_compact<<<dim3(nblk, nkeys), NSC_B, 0, ctx->stream>>>(d_flag, n, d_block, d_list);
   }
   ZK_HIP(hipGetLastError());
@@ -425,10 +371,7 @@ int zkmi_note_store_info(const zkmi_note_store* s, uint64_t out[4]) {
 int zkmi_note_store_append(zkmi_ctx* ctx, zkmi_note_store* s, size_t n, const uint32_t* positions,
                            const uint8_t* commitments, const uint8_t* ephemeral_pks, const uint8_t* nonces,
                            const uint32_t* ct_lens, const uint8_t* cts) {
-  if (!ctx || !s || s->ctx != ctx) {
-    set_error("zkmi_note_store_append: null context or store, or a store of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_note_store_append", "store", ctx, s ? s->ctx : nullptr)) return ZKMI_EINVAL;
   if (n == 0) return 0;
   if (!positions || !commitments || !ephemeral_pks || !nonces || !ct_lens) {
     set_error("zkmi_note_store_append: null argument");
@@ -486,10 +429,7 @@ int zkmi_note_store_append(zkmi_ctx* ctx, zkmi_note_store* s, size_t n, const ui
 int zkmi_note_store_get(zkmi_ctx* ctx, const zkmi_note_store* s, uint64_t first, size_t n, uint32_t* positions,
                         uint8_t* commitments, uint8_t* ephemeral_pks, uint8_t* nonces, uint32_t* ct_lens,
                         uint8_t* cts) {
-  if (!ctx || !s || s->ctx != ctx) {
-    set_error("zkmi_note_store_get: null context or store, or a store of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_note_store_get", "store", ctx, s ? s->ctx : nullptr)) return ZKMI_EINVAL;
   if (first > s->count || n > s->count - first) {
     set_error("zkmi_note_store_get: [%llu, +%zu) of a store of %llu notes", (unsigned long long)first, n,
               (unsigned long long)s->count);
@@ -526,10 +466,7 @@ int zkmi_note_scan(zkmi_ctx* ctx, const zkmi_note_store* s, const zkmi_mimc* mh,
                    uint32_t from_position, uint32_t limit, uint32_t* counts, uint32_t* scanned_to, uint32_t* stats,
                    uint32_t* positions, uint64_t* values, uint8_t* randomness, uint8_t* commitments,
                    uint32_t* memo_lens, uint8_t* memos) {
-  if (!ctx || !s || s->ctx != ctx) {
-    set_error("zkmi_note_scan: null context or store, or a store of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_note_scan", "store", ctx, s ? s->ctx : nullptr)) return ZKMI_EINVAL;
   if (scheme > 2 || nkeys > NSC_MAX_KEYS || limit < 1 || limit > NSC_MAX_LIMIT) {
     set_error("zkmi_note_scan: scheme %u (0..2), %zu keys (at most 64) or limit %u (1..65536)", scheme, nkeys, limit);
     return ZKMI_EINVAL;
@@ -537,8 +474,8 @@ int zkmi_note_scan(zkmi_ctx* ctx, const zkmi_note_store* s, const zkmi_mimc* mh,
   const Fe* table = nullptr;
   uint32_t half = 0, rounds = 0, nconst = 0;
   const zkmi_ctx* hctx = ctx;
-  if (scheme == 1 && mh) table = mimc_device_table(mh, &hctx);
-  if (scheme == 2 && ph) table = poseidon_device_table(ph, &half, &rounds, &nconst, &hctx);
+  if (scheme == 1 && mh) table = mh->d_table, hctx = mh->ctx;
+  if (scheme == 2 && ph) table = ph->d_table, half = ph->half, rounds = ph->rounds, nconst = ph->nconst, hctx = ph->ctx;
   if ((scheme != 0 && !table) || hctx != ctx) {
     set_error("zkmi_note_scan: scheme %u needs its hasher, made on this context", scheme);
     return ZKMI_EINVAL;

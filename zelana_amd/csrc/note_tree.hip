@@ -9,21 +9,8 @@
 
 #include <vector>
 
-#include "poseidon_hash.h"
-#include "zkmi_internal.h"
-
-struct zkmi_poseidon {
-  zkmi_ctx* ctx = nullptr;
-  uint32_t half = 0, rounds = 0, nconst = 0;
-  std::vector<zk::Fe> table;  // Montgomery form, host copy (the empty-subtree chain is made on the host)
-  // the quad mapping for launches of few hashes; off with ZKMI_DEBUG_NOTE_TREE_NO_QUAD=1
-  // at create (every launch then runs one lane per hash: tools/note_tree.py's A/B)
-  bool quad = true;
-  zk::Fe* d_table = nullptr;
-  ~zkmi_poseidon() {
-    if (d_table) (void)hipFree(d_table);
-  }
-};
+#include "hashers.h"
+#include "lane_util.h"
 
 struct zkmi_note_tree {
   zkmi_ctx* ctx = nullptr;
@@ -56,15 +43,6 @@ constexpr uint64_t NT_QUAD_MAX = 16384;
 static unsigned nt_blocks(uint64_t n) { return (unsigned)((n + NTB - 1) / NTB); }
 static bool nt_quad(const zkmi_poseidon* ph, uint64_t n) { return ph->quad && n <= NT_QUAD_MAX; }
 
-// the parameter set's table into LDS: every lane of a wave reads the same
-// constant at the same time (a broadcast read)
-__device__ __forceinline__ void posh_table_lds(Fe* pc_s, const Fe* __restrict__ pc, uint32_t nconst) {
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(pc);
-  uint32_t* dst = reinterpret_cast<uint32_t*>(pc_s);
-  for (uint32_t i = threadIdx.x; i < nconst * NL; i += blockDim.x) dst[i] = src[i];
-  __syncthreads();
-}
-
 // ------------------------------------------------------------ quad mapping
 // One permutation on a quad of lanes, the shape of wprog.hip's poseidon_quad
 // without its trace: lane q < 3 holds state element q (lane 3 mirrors lane 2
@@ -76,14 +54,6 @@ __device__ __forceinline__ void posh_table_lds(Fe* pc_s, const Fe* __restrict__ 
 // to fill the device (NT_QUAD_MAX), which is where latency is all there is:
 // the narrow levels of an append, the per-insertion roots of a short append,
 // a short hash_many.  All four lanes of a quad must be active.
-template <int LANE>
-__device__ __forceinline__ Fe quad_bcast(const Fe& x) {
-  constexpr int ctrl = LANE | (LANE << 2) | (LANE << 4) | (LANE << 6);  // quad_perm [L, L, L, L]
-  Fe r;
-#pragma unroll
-  for (int i = 0; i < NL; i++) r.v[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)x.v[i], ctrl, 0xF, 0xF, false);
-  return r;
-}
 // s: this lane's state element; qq = min(lane in quad, 2)
 __device__ __forceinline__ void posh_permute_quad(Fe& s, uint32_t qq, const Fe* pc, uint32_t half, uint32_t rounds) {
   const Fe* row = pc + 3 * rounds + 3 * qq;
@@ -100,11 +70,11 @@ __device__ __forceinline__ void posh_sponge_quad(const uint32_t* in, uint32_t ar
   const uint32_t qq = q < 3 ? q : 2;
   Fe s = fe_zero();
   for (uint32_t c = 0; c < arity; c += 2) {
-    if (qq == 1) s = add<FrP>(s, posh_in(in + 8 * c));
-    if (qq == 2 && c + 1 < arity) s = add<FrP>(s, posh_in(in + 8 * c + 8));
+    if (qq == 1) s = add<FrP>(s, fr_in(in + 8 * c));
+    if (qq == 2 && c + 1 < arity) s = add<FrP>(s, fr_in(in + 8 * c + 8));
     posh_permute_quad(s, qq, pc, half, rounds);
   }
-  if (q == 1) posh_out(out, s);
+  if (q == 1) fr_out(out, s);
 }
 // nt_rehash on a quad
 __device__ __forceinline__ void nt_rehash_quad(uint32_t* tree, const uint32_t* empty, const NtGeom& g, uint32_t l,
@@ -112,31 +82,31 @@ __device__ __forceinline__ void nt_rehash_quad(uint32_t* tree, const uint32_t* e
                                                uint32_t rounds) {
   const uint32_t qq = q < 3 ? q : 2;
   Fe s = fe_zero();
-  if (qq == 1) s = posh_in(tree + (g.off[l - 1] + 2 * p) * 8);
-  if (qq == 2) s = posh_in(nt_node(tree, empty, g, l - 1, 2 * p + 1, next));
+  if (qq == 1) s = fr_in(tree + (g.off[l - 1] + 2 * p) * 8);
+  if (qq == 2) s = fr_in(nt_node(tree, empty, g, l - 1, 2 * p + 1, next));
   posh_permute_quad(s, qq, pc, half, rounds);
-  if (q == 1) posh_out(tree + (g.off[l] + p) * 8, s);
+  if (q == 1) fr_out(tree + (g.off[l] + p) * 8, s);
 }
 // nt_root_after on a quad: the carried node is broadcast from lane 1 after every level
 __device__ __forceinline__ void nt_root_after_quad(const uint32_t* tree, const uint32_t* empty, const NtGeom& g,
                                                    uint64_t k, uint32_t* out, uint32_t q, const Fe* pc,
                                                    uint32_t half, uint32_t rounds) {
   const uint32_t qq = q < 3 ? q : 2;
-  Fe cur = posh_in(tree + (g.off[0] + k) * 8);
+  Fe cur = fr_in(tree + (g.off[0] + k) * 8);
   uint64_t idx = k;
   for (uint32_t l = 0; l < g.depth; l++, idx >>= 1) {
     Fe s = fe_zero();
     if (idx & 1) {
-      if (qq == 1) s = posh_in(tree + (g.off[l] + idx - 1) * 8);
+      if (qq == 1) s = fr_in(tree + (g.off[l] + idx - 1) * 8);
       if (qq == 2) s = cur;
     } else {
       if (qq == 1) s = cur;
-      if (qq == 2) s = posh_in(empty + 8 * l);
+      if (qq == 2) s = fr_in(empty + 8 * l);
     }
     posh_permute_quad(s, qq, pc, half, rounds);
     cur = quad_bcast<1>(s);
   }
-  if (q == 1) posh_out(out, cur);
+  if (q == 1) fr_out(out, cur);
 }
 
 // ----------------------------------------------------------------- kernels
@@ -149,7 +119,7 @@ __global__ void __launch_bounds__(NTB) k_posh_hash_many(const Fe* __restrict__ p
                                                         uint32_t rounds, const uint32_t* __restrict__ in,
                                                         uint32_t* __restrict__ out, size_t n, uint32_t arity) {
   __shared__ Fe pc_s[POSH_MAX_NCONST];
-  posh_table_lds(pc_s, pc, nconst);
+  fe_table_lds(pc_s, pc, nconst);
   const size_t t = blockIdx.x * (size_t)NTB + threadIdx.x, i = QUAD ? t >> 2 : t;
   if (i >= n) return;
   if (QUAD) posh_sponge_quad(in + i * arity * 8, arity, out + i * 8, threadIdx.x & 3, pc_s, half, rounds);
@@ -161,7 +131,7 @@ __global__ void __launch_bounds__(NTB) k_nt_leaves(const uint32_t* __restrict__ 
                                                    uint64_t first, uint64_t n) {
   const uint64_t i = blockIdx.x * (uint64_t)NTB + threadIdx.x;
   if (i >= n) return;
-  posh_canon(raw + i * 8, level0 + (first + i) * 8);
+  fr_canon(raw + i * 8, level0 + (first + i) * 8);
 }
 
 // one wide level: the nodes [lo, lo + cnt) of level l
@@ -171,7 +141,7 @@ __global__ void __launch_bounds__(NTB) k_nt_level(uint32_t* tree, const uint32_t
                                                   uint64_t cnt, uint64_t next, const Fe* __restrict__ pc,
                                                   uint32_t nconst, uint32_t half, uint32_t rounds) {
   __shared__ Fe pc_s[POSH_MAX_NCONST];
-  posh_table_lds(pc_s, pc, nconst);
+  fe_table_lds(pc_s, pc, nconst);
   const uint64_t t = blockIdx.x * (uint64_t)NTB + threadIdx.x, i = QUAD ? t >> 2 : t;
   if (i >= cnt) return;
   if (QUAD) nt_rehash_quad(tree, empty, *geom, l, lo + i, next, threadIdx.x & 3, pc_s, half, rounds);
@@ -189,10 +159,10 @@ __global__ void __launch_bounds__(NTB) k_nt_tail(uint32_t* tree, const uint32_t*
                                                  const Fe* __restrict__ pc, uint32_t nconst, uint32_t half,
                                                  uint32_t rounds) {
   __shared__ Fe pc_s[POSH_MAX_NCONST];
-  posh_table_lds(pc_s, pc, nconst);
+  fe_table_lds(pc_s, pc, nconst);
   const uint32_t depth = geom->depth;
   if (raw) {
-    for (uint64_t t = threadIdx.x; t < n; t += NTB) posh_canon(raw + t * 8, tree + (geom->off[0] + first + t) * 8);
+    for (uint64_t t = threadIdx.x; t < n; t += NTB) fr_canon(raw + t * 8, tree + (geom->off[0] + first + t) * 8);
     __syncthreads();
   }
   for (uint32_t l = l0; l <= depth; l++) {
@@ -217,7 +187,7 @@ __global__ void __launch_bounds__(NTB) k_nt_roots(const uint32_t* __restrict__ t
                                                   uint32_t* __restrict__ roots, const Fe* __restrict__ pc,
                                                   uint32_t nconst, uint32_t half, uint32_t rounds) {
   __shared__ Fe pc_s[POSH_MAX_NCONST];
-  posh_table_lds(pc_s, pc, nconst);
+  fe_table_lds(pc_s, pc, nconst);
   const uint64_t t = blockIdx.x * (uint64_t)NTB + threadIdx.x, k = QUAD ? t >> 2 : t;
   if (k >= n) return;
   if (QUAD) nt_root_after_quad(tree, empty, *geom, first + k, roots + k * 8, threadIdx.x & 3, pc_s, half, rounds);
@@ -234,30 +204,20 @@ __global__ void __launch_bounds__(NTB) k_nt_paths(const uint32_t* __restrict__ t
   if (t >= n * depth) return;
   const uint64_t i = t / depth;
   const uint32_t l = (uint32_t)(t % depth);
-  const uint32_t* src = nt_sibling(tree, empty, *geom, l, pos[i], next);
-#pragma unroll
-  for (int w = 0; w < 8; w++) sib[t * 8 + w] = src[w];
+  copy8(sib + t * 8, nt_sibling(tree, empty, *geom, l, pos[i], next));
 }
 
 static int posh_hash_many(zkmi_ctx* ctx, const zkmi_poseidon* ph, size_t n, uint32_t arity, const uint64_t* in,
                           uint64_t* out) {
-  uint32_t *d_in, *d_out;
-  ZK_TRY(ctx->ws.get("ph_in", n * arity * 32, (void**)&d_in));
-  ZK_TRY(ctx->ws.get("ph_out", n * 32, (void**)&d_out));
-  ZK_HIP(hipMemcpyAsync(d_in, in, n * arity * 32, hipMemcpyHostToDevice, ctx->stream));
-  {
-    ScopedKernelTimer tm(ctx, "poseidon_hash_many");
+  return hasher_hash_many(ctx, "ph_in", "ph_out", "poseidon_hash_many", n, arity, in, out,
+                          [&](const uint32_t* d_in, uint32_t* d_out) {
     if (nt_quad(ph, n))
       k_posh_hash_many<true><<<nt_blocks(4 * n), NTB, 0, ctx->stream>>>(ph->d_table, ph->nconst, ph->half, ph->rounds,
                                                                        d_in, d_out, n, arity);
     else
       k_posh_hash_many<false><<<nt_blocks(n), NTB, 0, ctx->stream>>>(ph->d_table, ph->nconst, ph->half, ph->rounds,
                                                                     d_in, d_out, n, arity);
-  }
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  ZK_HIP(hipStreamSynchronize(ctx->stream));
-  return timer_flush(ctx);
+  });
 }
 
 static int note_tree_append(zkmi_ctx* ctx, zkmi_note_tree* t, size_t n, const uint64_t* leaves, uint64_t* roots) {
@@ -321,13 +281,6 @@ static int note_tree_append(zkmi_ctx* ctx, zkmi_note_tree* t, size_t n, const ui
   return 0;
 }
 
-// the hasher's resident table, rounds and context, for the other users of a zkmi_poseidon (note_scan.hip)
-const Fe* poseidon_device_table(const zkmi_poseidon* ph, uint32_t* half, uint32_t* rounds, uint32_t* nconst,
-                                const zkmi_ctx** ctx) {
-  *half = ph->half, *rounds = ph->rounds, *nconst = ph->nconst, *ctx = ph->ctx;
-  return ph->d_table;
-}
-
 }  // namespace zk
 
 using namespace zk;
@@ -355,19 +308,10 @@ int zkmi_poseidon_create(zkmi_ctx* ctx, uint32_t full_rounds, uint32_t partial_r
   ph->quad = !(no_quad && no_quad[0] == '1');
   ph->table.resize(ph->nconst);
   posh_table(reinterpret_cast<const uint32_t*>(consts), ph->nconst, ph->table.data());
-  if (hipMalloc((void**)&ph->d_table, ph->nconst * sizeof(Fe)) != hipSuccess) {
-    (void)hipGetLastError();
+  const int rc = hasher_upload_table("zkmi_poseidon_create", ctx, ph->table.data(), ph->nconst, &ph->d_table);
+  if (rc != 0) {
     delete ph;
-    set_error("zkmi_poseidon_create: hipMalloc failed");
-    return ZKMI_ENOMEM;
-  }
-  hipError_t e = hipMemcpyAsync(ph->d_table, ph->table.data(), ph->nconst * sizeof(Fe), hipMemcpyHostToDevice,
-                                ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    delete ph;
-    set_error("zkmi_poseidon_create: upload failed (%s)", hipGetErrorString(e));
-    return ZKMI_EHIP;
+    return rc;
   }
   *out = ph;
   return 0;
@@ -380,10 +324,7 @@ void zkmi_poseidon_destroy(zkmi_poseidon* ph) {
 
 int zkmi_poseidon_hash_many(zkmi_ctx* ctx, const zkmi_poseidon* ph, size_t n, uint32_t arity, const uint64_t* in,
                             uint64_t* out) {
-  if (!ctx || !ph || ph->ctx != ctx) {
-    set_error("zkmi_poseidon_hash_many: null context or hasher, or a hasher of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_poseidon_hash_many", "hasher", ctx, ph ? ph->ctx : nullptr)) return ZKMI_EINVAL;
   if (arity < 1 || arity > 4) {
     set_error("zkmi_poseidon_hash_many: arity %u outside 1..4", arity);
     return ZKMI_EINVAL;
@@ -418,7 +359,7 @@ int zkmi_note_tree_create(zkmi_ctx* ctx, const zkmi_poseidon* ph, uint32_t depth
   t->depth = depth;
   t->capacity = capacity;
   nt_geom(t->geom, depth, capacity);
-  posh_canon(reinterpret_cast<const uint32_t*>(empty_leaf), t->empty);
+  fr_canon(reinterpret_cast<const uint32_t*>(empty_leaf), t->empty);
   for (uint32_t l = 0; l < depth; l++)
     posh_pair(t->empty + 8 * l, t->empty + 8 * l, t->empty + 8 * l + 8, ph->table.data(), ph->half, ph->rounds);
   memcpy(t->root, t->empty + 8 * depth, 32);
@@ -460,10 +401,7 @@ int zkmi_note_tree_info(const zkmi_note_tree* t, uint64_t out[3]) {
 
 int zkmi_note_tree_append(zkmi_ctx* ctx, zkmi_note_tree* t, size_t n, const uint64_t* leaves, uint64_t* first,
                           uint64_t* roots) {
-  if (!ctx || !t || t->ctx != ctx) {
-    set_error("zkmi_note_tree_append: null context or tree, or a tree of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_note_tree_append", "tree", ctx, t ? t->ctx : nullptr)) return ZKMI_EINVAL;
   if (n > t->capacity - t->next) {
     set_error("zkmi_note_tree_append: %zu leaves onto %llu of a capacity of %llu", n, (unsigned long long)t->next,
               (unsigned long long)t->capacity);
@@ -490,10 +428,7 @@ int zkmi_note_tree_root(zkmi_ctx* ctx, const zkmi_note_tree* t, uint64_t out[4])
 
 int zkmi_note_tree_paths(zkmi_ctx* ctx, const zkmi_note_tree* t, size_t n, const uint64_t* positions,
                          uint64_t* siblings) {
-  if (!ctx || !t || t->ctx != ctx) {
-    set_error("zkmi_note_tree_paths: null context or tree, or a tree of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_note_tree_paths", "tree", ctx, t ? t->ctx : nullptr)) return ZKMI_EINVAL;
   if (n == 0) return 0;
   if (!positions || !siblings) {
     set_error("zkmi_note_tree_paths: null argument");
@@ -525,10 +460,7 @@ int zkmi_note_tree_paths(zkmi_ctx* ctx, const zkmi_note_tree* t, size_t n, const
 }
 
 int zkmi_note_tree_leaves(zkmi_ctx* ctx, const zkmi_note_tree* t, uint64_t first, size_t n, uint64_t* out) {
-  if (!ctx || !t || t->ctx != ctx) {
-    set_error("zkmi_note_tree_leaves: null context or tree, or a tree of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_note_tree_leaves", "tree", ctx, t ? t->ctx : nullptr)) return ZKMI_EINVAL;
   if (n == 0) return 0;
   if (first >= t->next || n > t->next - first) {
     set_error("zkmi_note_tree_leaves: [%llu, +%zu) of a tree of %llu leaves", (unsigned long long)first, n,

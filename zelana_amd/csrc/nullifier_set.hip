@@ -5,6 +5,7 @@
 // context stream, and every call returns with its results on the host.
 #include <string.h>
 
+#include "lane_util.h"
 #include "nullifier_set.h"
 #include "zkmi_internal.h"
 
@@ -171,39 +172,11 @@ __global__ void __launch_bounds__(NSB) k_ns_reasons(const uint32_t* __restrict__
   if (threadIdx.x == 0) block_acc[blockIdx.x] = (uint32_t)n;
 }
 
-// block_acc -> its exclusive prefix sums, in place; the total to the counter.
-// One workgroup: a lane sums a run of blocks, the lanes' sums are scanned in LDS.
-__global__ void __launch_bounds__(NSB) k_ns_scan(uint32_t* block_acc, uint32_t nblocks, uint32_t* ctr) {
-  __shared__ uint32_t sum_s[NSB];
-  const uint32_t per = (nblocks + NSB - 1) / NSB;
-  const uint32_t lo = threadIdx.x * per < nblocks ? threadIdx.x * per : nblocks;
-  const uint32_t hi = lo + per < nblocks ? lo + per : nblocks;
-  uint32_t s = 0;
-  for (uint32_t b = lo; b < hi; b++) s += block_acc[b];
-  sum_s[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t run = 0;
-    for (int i = 0; i < NSB; i++) {
-      const uint32_t v = sum_s[i];
-      sum_s[i] = run;
-      run += v;
-    }
-    ctr[NS_C_ACCEPTED] = run;
-  }
-  __syncthreads();
-  uint32_t run = sum_s[threadIdx.x];
-  for (uint32_t b = lo; b < hi; b++) {
-    const uint32_t v = block_acc[b];
-    block_acc[b] = run;
-    run += v;
-  }
-}
-
-// Insert, one lane per transfer (the blocks of k_ns_reasons): accepted
-// transfer t, the rank-th accepted one of the call, writes its keys to the log
-// at count + rank per_tx + k and enters them in the table.  No two inserted
-// keys are equal and none is stored, so ns_insert claims without comparing.
+// Insert, one lane per transfer (the blocks of k_ns_reasons, block_acc turned
+// into offsets by k_block_offsets): accepted transfer t, the rank-th accepted
+// one of the call, writes its keys to the log at count + rank per_tx + k and
+// enters them in the table.  No two inserted keys are equal and none is
+// stored, so ns_insert claims without comparing.
 __global__ void __launch_bounds__(NSB) k_ns_insert(uint32_t* table, uint64_t slots, uint32_t* log, uint64_t count,
                                                    const uint32_t* __restrict__ keys,
                                                    const uint32_t* __restrict__ state,
@@ -212,13 +185,8 @@ __global__ void __launch_bounds__(NSB) k_ns_insert(uint32_t* table, uint64_t slo
   __shared__ uint32_t wave_s[NSB / 64];
   const uint32_t t = blockIdx.x * NSB + threadIdx.x;
   const bool ins = t < ntx && state[t] == NS_ST_ACCEPTED;
-  const unsigned long long m = __ballot(ins);
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wave_s[wave] = (uint32_t)__popcll(m);
-  __syncthreads();
+  const uint32_t rank = block_rank<NSB>(ins, block_off + blockIdx.x, wave_s);
   if (!ins) return;
-  uint32_t rank = block_off[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-  for (uint32_t w = 0; w < wave; w++) rank += wave_s[w];
   for (uint32_t k = 0; k < per_tx; k++) {
     const NsKey key = ns_load(keys + 8 * ((uint64_t)t * per_tx + k));
     const uint64_t index = count + (uint64_t)rank * per_tx + k;
@@ -305,7 +273,7 @@ static int ns_spend(zkmi_ctx* ctx, zkmi_nullifier_set* s, uint32_t ntx, uint32_t
     ScopedKernelTimer tm(ctx, "nullifier_set_reasons");
     k_ns_reasons<<<nblocks, NSB, 0, ctx->stream>>>(d_state, d_flags, d_group, d_acc, ntx, per_tx, d_verdict, d_detail,
                                                    d_block);
-    k_ns_scan<<<1, NSB, 0, ctx->stream>>>(d_block, nblocks, d_ctr);
+    k_block_offsets<NSB><<<1, NSB, 0, ctx->stream>>>(d_block, nblocks, d_ctr + NS_C_ACCEPTED);
   }
   ZK_HIP(hipGetLastError());
   ZK_HIP(hipMemcpyAsync(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, ctx->stream));
@@ -405,10 +373,7 @@ int zkmi_nullifier_set_info(const zkmi_nullifier_set* s, uint64_t out[3]) {
 
 int zkmi_nullifier_set_contains(zkmi_ctx* ctx, const zkmi_nullifier_set* s, size_t n, const uint8_t* keys,
                                 uint8_t* out) {
-  if (!ctx || !s || s->ctx != ctx) {
-    set_error("zkmi_nullifier_set_contains: null context or set, or a set of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_nullifier_set_contains", "set", ctx, s ? s->ctx : nullptr)) return ZKMI_EINVAL;
   if (n > NS_MAX_CALL_KEYS) {
     set_error("zkmi_nullifier_set_contains: %zu keys in one call (at most 2^24)", n);
     return ZKMI_EINVAL;
@@ -424,10 +389,7 @@ int zkmi_nullifier_set_contains(zkmi_ctx* ctx, const zkmi_nullifier_set* s, size
 
 int zkmi_nullifier_set_spend(zkmi_ctx* ctx, zkmi_nullifier_set* s, size_t ntx, uint32_t per_tx, const uint8_t* keys,
                              const uint8_t* eligible, uint32_t* verdict, uint32_t* detail, uint32_t* rounds) {
-  if (!ctx || !s || s->ctx != ctx) {
-    set_error("zkmi_nullifier_set_spend: null context or set, or a set of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_nullifier_set_spend", "set", ctx, s ? s->ctx : nullptr)) return ZKMI_EINVAL;
   if (per_tx < 1 || per_tx > NS_MAX_PER_TX) {
     set_error("zkmi_nullifier_set_spend: per_tx %u outside 1..%u", per_tx, NS_MAX_PER_TX);
     return ZKMI_EINVAL;
@@ -449,10 +411,7 @@ int zkmi_nullifier_set_spend(zkmi_ctx* ctx, zkmi_nullifier_set* s, size_t ntx, u
 }
 
 int zkmi_nullifier_set_log(zkmi_ctx* ctx, const zkmi_nullifier_set* s, uint64_t first, size_t n, uint8_t* out) {
-  if (!ctx || !s || s->ctx != ctx) {
-    set_error("zkmi_nullifier_set_log: null context or set, or a set of another context");
-    return ZKMI_EINVAL;
-  }
+  if (!zk_owned("zkmi_nullifier_set_log", "set", ctx, s ? s->ctx : nullptr)) return ZKMI_EINVAL;
   if (first > s->count || n > s->count - first) {
     set_error("zkmi_nullifier_set_log: [%llu, +%zu) of a log of %llu keys", (unsigned long long)first, n,
               (unsigned long long)s->count);

@@ -67,14 +67,8 @@ ZK_HD Fe posh_mul3(const Fe& a0, const Fe& b0, const Fe& a1, const Fe& b1, const
   return r;
 }
 
-// Fr with compiler-scheduled products (ff.h's FqPn for Fr): the compiler
-// splits a column's chain of mads into parallel partial sums, which costs
-// adds and wins where a lone wave on a SIMD sees the latency of every mad
-struct FrPn : FrP {
-  static constexpr bool ASM = false;
-};
-// x^5.  P = FrP: one-chain mads, for kernels that fill the device; FrPn: for
-// the latency-bound ones
+// x^5.  P = FrP: one-chain mads, for kernels that fill the device; ff.h's
+// FrPn: for the latency-bound ones
 template <class P = FrP>
 ZK_HD Fe posh_sbox(const Fe& t) {
   const Fe x2 = sqr<P>(t);
@@ -100,23 +94,6 @@ ZK_HD void posh_permute(Fe s[3], const Fe* pc, uint32_t half, uint32_t rounds) {
   }
 }
 
-// any 256-bit value -> Montgomery form of the value mod r (2^256 < 8r, what
-// ff.h's product accepts)
-ZK_HD Fe posh_in(const uint32_t* w) {
-  uint32_t x[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) x[i] = w[i];
-  return to_mont<FrP>(unpack(x));
-}
-ZK_HD void posh_out(uint32_t* w, const Fe& a) {
-  uint32_t x[8];
-  pack(x, from_mont<FrP>(a));
-#pragma unroll
-  for (int i = 0; i < 8; i++) w[i] = x[i];
-}
-// any 256-bit value -> the canonical words of the value mod r
-ZK_HD void posh_canon(const uint32_t* in, uint32_t* out) { posh_out(out, posh_in(in)); }
-
 // absorb(x_0 .. x_{arity-1}); squeeze_field_elements(1)[0] of the duplex
 // sponge, arity 1..4: inputs are added to state[1], state[2]; the sponge
 // permutes when the rate is full and before the squeeze, that is once per
@@ -125,22 +102,22 @@ ZK_HD void posh_sponge(const uint32_t* in, uint32_t arity, uint32_t* out, const 
                        uint32_t rounds) {
   Fe s[3] = {fe_zero(), fe_zero(), fe_zero()};
   for (uint32_t c = 0; c < arity; c += 2) {
-    s[1] = add<FrP>(s[1], posh_in(in + 8 * c));
-    if (c + 1 < arity) s[2] = add<FrP>(s[2], posh_in(in + 8 * c + 8));
+    s[1] = add<FrP>(s[1], fr_in(in + 8 * c));
+    if (c + 1 < arity) s[2] = add<FrP>(s[2], fr_in(in + 8 * c + 8));
     posh_permute(s, pc, half, rounds);
   }
-  posh_out(out, s[1]);
+  fr_out(out, s[1]);
 }
 // H(left, right): the tree's node hash
 ZK_HD void posh_pair(const uint32_t* left, const uint32_t* right, uint32_t* out, const Fe* pc, uint32_t half,
                      uint32_t rounds) {
-  Fe s[3] = {fe_zero(), posh_in(left), posh_in(right)};
+  Fe s[3] = {fe_zero(), fr_in(left), fr_in(right)};
   posh_permute(s, pc, half, rounds);
-  posh_out(out, s[1]);
+  fr_out(out, s[1]);
 }
 // the table of a parameter set from its canonical constants (n x 8 words)
 ZK_HD void posh_table(const uint32_t* canon, uint32_t n, Fe* pc) {
-  for (uint32_t i = 0; i < n; i++) pc[i] = reduce<FrP>(posh_in(canon + 8 * i));
+  for (uint32_t i = 0; i < n; i++) pc[i] = reduce<FrP>(fr_in(canon + 8 * i));
 }
 
 // ------------------------------------------------------------------ the tree
@@ -197,22 +174,22 @@ ZK_HD void nt_rehash(uint32_t* tree, const uint32_t* empty, const NtGeom& g, uin
 // holds only later leaves and was e_l at the time.
 ZK_HD void nt_root_after(const uint32_t* tree, const uint32_t* empty, const NtGeom& g, uint64_t k, uint32_t* out,
                          const Fe* pc, uint32_t half, uint32_t rounds) {
-  Fe cur = posh_in(tree + (g.off[0] + k) * 8);
+  Fe cur = fr_in(tree + (g.off[0] + k) * 8);
   uint64_t idx = k;
   for (uint32_t l = 0; l < g.depth; l++, idx >>= 1) {
     Fe s[3];
     s[0] = fe_zero();
     if (idx & 1) {
-      s[1] = posh_in(tree + (g.off[l] + idx - 1) * 8);
+      s[1] = fr_in(tree + (g.off[l] + idx - 1) * 8);
       s[2] = cur;
     } else {
       s[1] = cur;
-      s[2] = posh_in(empty + 8 * l);
+      s[2] = fr_in(empty + 8 * l);
     }
     posh_permute(s, pc, half, rounds);
     cur = s[1];
   }
-  posh_out(out, cur);
+  fr_out(out, cur);
 }
 // sibling of the path of leaf `position` at level l, in a tree of `next` leaves
 ZK_HD const uint32_t* nt_sibling(const uint32_t* tree, const uint32_t* empty, const NtGeom& g, uint32_t l,

@@ -54,6 +54,7 @@
 
 #include "dev_io.h"
 #include "ff.h"
+#include "lane_util.h"
 
 #include "zkmi_internal.h"
 
@@ -316,14 +317,6 @@ __device__ __forceinline__ void st_raw(uint32_t* z, uint32_t var, const Fe& v) {
   p[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
-template <int LANE>
-__device__ __forceinline__ Fe quad_bcast(const Fe& x) {
-  constexpr int ctrl = LANE | (LANE << 2) | (LANE << 4) | (LANE << 6);  // quad_perm [L, L, L, L]
-  Fe r;
-#pragma unroll
-  for (int i = 0; i < NL; i++) r.v[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)x.v[i], ctrl, 0xF, 0xF, false);
-  return r;
-}
 __device__ __forceinline__ Fe sel(bool c, const Fe& a, const Fe& b) {
   Fe r;
 #pragma unroll

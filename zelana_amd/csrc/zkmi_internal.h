@@ -209,6 +209,16 @@ inline int dev_of(const zkmi_ctx* c) { return c ? c->device : -1; }
 inline int dev_of(const zkmi_bases* b) { return b && b->ctx ? b->ctx->device : -1; }
 #define ZK_DEVICE_GUARD(obj) ::zk::DeviceGuard zk_device_guard_(::zk::dev_of(obj))
 
+// The handle check of an entry point fn that works on a `what` (a tree, a
+// set, ...) made on a context: true when ctx is given and is the handle's;
+// otherwise false, with the message set.  owner_or_null: the handle's context,
+// null for a null handle.
+inline bool zk_owned(const char* fn, const char* what, const zkmi_ctx* ctx, const zkmi_ctx* owner_or_null) {
+  if (ctx && owner_or_null == ctx) return true;
+  set_error("%s: null context or %s, or a %s of another context", fn, what, what);
+  return false;
+}
+
 // kernel timing helpers (events on ctx->stream)
 void timer_begin(zkmi_ctx* ctx, const char* name, hipEvent_t* ev, hipStream_t st);
 void timer_end(zkmi_ctx* ctx, const char* name, hipEvent_t ev, hipStream_t st);

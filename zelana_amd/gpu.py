@@ -65,12 +65,46 @@ class DeviceView(DeviceBuffer):
         self.ptr = vp()
 
 
-class Bases:
-    def __init__(self, ctx: "Context", points, g2: bool, *, generate_seed=None, n=None, first=0):
+class _Handle:
+    """A native object made on a Context: `h` is its handle, `_destroy` names
+    the entry point that frees it.  The context closes the objects it still
+    tracks before it goes, so close() may run more than once."""
+    _destroy = ""
+
+    def _open(self, ctx: "Context"):
+        self.h = vp()
         ctx._track(self)
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._destroy)(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _positions(positions) -> np.ndarray:
+    """tree positions for the C ABI: a contiguous u64 array"""
+    return np.ascontiguousarray(np.asarray(list(positions), np.uint64))
+
+
+def _outbuf(n: int, *shape, dtype=np.uint64) -> np.ndarray:
+    """A zeroed output array of n rows of `shape`, never empty (the C ABI takes
+    no null output pointer for n = 0): callers hand back its [:n]."""
+    return np.zeros((max(n, 1),) + shape, dtype)
+
+
+class Bases(_Handle):
+    _destroy = "zkmi_bases_destroy"
+
+    def __init__(self, ctx: "Context", points, g2: bool, *, generate_seed=None, n=None, first=0):
+        self._open(ctx)
         if generate_seed is not None:
             self.ctx, self.g2, self.n = ctx, g2, n
-            self.h = vp()
             if first:
                 assert not g2, "ranged generation is G1 only"
                 check(lib().zkmi_bases_generate_range_g1(ctx.h, generate_seed, first, n, ctypes.byref(self.h)),
@@ -82,7 +116,6 @@ class Bases:
         pts = np.ascontiguousarray(points, dtype=np.uint64)
         assert pts.ndim == 2 and pts.shape[1] == (16 if g2 else 8)
         self.ctx, self.g2, self.n = ctx, g2, pts.shape[0]
-        self.h = vp()
         f = lib().zkmi_bases_create_g2 if g2 else lib().zkmi_bases_create_g1
         check(f(ctx.h, _p64(pts), self.n, ctypes.byref(self.h)), "zkmi_bases_create")
 
@@ -101,17 +134,6 @@ class Bases:
         out = np.zeros((self.n, 16 if self.g2 else 8), np.uint64)
         check(lib().zkmi_bases_export(self.h, _p64(out)), "zkmi_bases_export")
         return out
-
-    def close(self):
-        if self.h:
-            lib().zkmi_bases_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Context:
@@ -214,8 +236,8 @@ class Context:
         """Bases P_i = P0 + (first + i) * D generated in HBM (SURVEY.md §8d's
         point stream; P0, D canonical affine, 8 u64 each)."""
         b = Bases.__new__(Bases)
-        b.ctx, b.g2, b.n, b.h = self, False, n, vp()
-        self._track(b)
+        b.ctx, b.g2, b.n = self, False, n
+        b._open(self)
         p0 = np.ascontiguousarray(p0, np.uint64)
         d = np.ascontiguousarray(d, np.uint64)
         check(lib().zkmi_bases_generate_arith_g1(self.h, _p64(p0), _p64(d), first, n, ctypes.byref(b.h)),
@@ -321,7 +343,7 @@ def comm_unique_id() -> bytes:
     return bytes(buf)
 
 
-class Comm:
+class Comm(_Handle):
     """Multi-rank communicator of a context (zkmi.h multi-GPU section).
 
     Comm.rccl(ctx, uid, nranks, rank): RCCL transport (one rank per GPU).
@@ -329,11 +351,12 @@ class Comm:
     -> list[bytes]` of every rank (e.g. torch.distributed over gloo), for
     ranks that share a GPU or hosts without RCCL."""
 
+    _destroy = "zkmi_comm_destroy"
+
     def __init__(self, ctx: Context):
         self.ctx = ctx
-        self.h = vp()
         self._cb = None
-        ctx._track(self)
+        self._open(ctx)
 
     @classmethod
     def rccl(cls, ctx: Context, uid: bytes, nranks: int, rank: int) -> "Comm":
@@ -390,17 +413,6 @@ class Comm:
     def msm_windows(self, bases: "Bases", dscalars: "DeviceBuffer", n: int, offset: int = 0):
         return self.ctx.msm_wait(self.msm_windows_submit(bases, dscalars, n, offset))
 
-    def close(self):
-        if self.h:
-            lib().zkmi_comm_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def g1_add(a, b):
     out = np.zeros(8, np.uint64)
@@ -430,13 +442,13 @@ def r1cs_struct(cs):
     return s, keep
 
 
-class ProvingKey:
+class ProvingKey(_Handle):
     """arkworks ProvingKey<Bn254> resident on the GPU (zkmi_pk_load)."""
+    _destroy = "zkmi_pk_destroy"
 
     def __init__(self, ctx: Context, pk_bytes: bytes, compressed: bool = True):
         self.ctx = ctx
-        self.h = vp()
-        ctx._track(self)
+        self._open(ctx)
         buf = np.frombuffer(pk_bytes, np.uint8)  # (read only: zkmi_pk_load takes a const pointer; no host copy)
         check(lib().zkmi_pk_load(ctx.h, buf.ctypes.data_as(u8p), len(pk_bytes), int(compressed),
                                  ctypes.byref(self.h)), "zkmi_pk_load")
@@ -480,8 +492,7 @@ class ProvingKey:
         tw = np.concatenate([_limbs(v) for v in toxic])
         pk = cls.__new__(cls)
         pk.ctx = ctx
-        pk.h = vp()
-        ctx._track(pk)
+        pk._open(ctx)
         check(lib().zkmi_groth16_setup(ctx.h, ctypes.byref(st), _p64(tw), _p64(np.ascontiguousarray(g1, np.uint64)),
                                        _p64(np.ascontiguousarray(g2, np.uint64)), ctypes.byref(pk.h)),
               "zkmi_groth16_setup")
@@ -490,17 +501,6 @@ class ProvingKey:
         check(lib().zkmi_pk_info(pk.h, _p64(info)))
         pk.n, pk.num_instance, pk.num_witness = (int(x) for x in info)
         return pk
-
-    def close(self):
-        if self.h:
-            lib().zkmi_pk_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def vk_canonical(ctx: Context, vk_bytes: bytes) -> bytes:
@@ -556,30 +556,19 @@ def groth16_verify(vk_bytes: bytes, public_inputs, a, b, c) -> bool:
     return bool(ok.value)
 
 
-class VerifyingKey:
+class VerifyingKey(_Handle):
     """arkworks-compressed VerifyingKey decoded and validated once
     (zkmi_vk_load), for groth16_verify_many.  A bad key raises ZkmiError."""
+    _destroy = "zkmi_vk_destroy"
 
     def __init__(self, ctx: Context, vk_bytes: bytes):
         self.ctx = ctx
-        self.h = vp()
-        ctx._track(self)
+        self._open(ctx)
         buf = np.frombuffer(bytes(vk_bytes), np.uint8)
         check(lib().zkmi_vk_load(ctx.h, buf.ctypes.data_as(u8p), buf.size, ctypes.byref(self.h)), "zkmi_vk_load")
         info = np.zeros(1, np.uint64)
         check(lib().zkmi_vk_info(self.h, _p64(info)), "zkmi_vk_info")
         self.n_inputs = int(info[0])
-
-    def close(self):
-        if self.h:
-            lib().zkmi_vk_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def groth16_verify_many(ctx: Context, vk: VerifyingKey, proofs, inputs, rho=None):
@@ -597,7 +586,7 @@ def groth16_verify_many(ctx: Context, vk: VerifyingKey, proofs, inputs, rho=None
         if any(not 0 <= int(v) < 1 << 128 for v in rho):
             raise ValueError("weights are 128-bit values")
         w = np.array([[int(v) & (2**64 - 1), int(v) >> 64] for v in rho], np.uint64).reshape(nb, 2)
-    valid = np.zeros(max(nb, 1), np.uint8)
+    valid = _outbuf(nb, dtype=np.uint8)
     st = VerifyStatsStruct()
     check(lib().zkmi_groth16_verify_many(ctx.h, vk.h, nb, _p64(ins), _p64(a), _p64(b), _p64(c),
                                          None if w is None else _p64(w), valid.ctypes.data_as(u8p), ctypes.byref(st)),
@@ -625,7 +614,7 @@ def groth16_verify_each(ctx: Context, vk: VerifyingKey, proofs, inputs):
     "invalid_points"})."""
     nb = len(proofs)
     a, b, c, ins = _proof_arrays(vk, proofs, inputs)
-    valid = np.zeros(max(nb, 1), np.uint8)
+    valid = _outbuf(nb, dtype=np.uint8)
     st = VerifyStatsStruct()
     check(lib().zkmi_groth16_verify_each(ctx.h, vk.h, nb, _p64(ins), _p64(a), _p64(b), _p64(c),
                                          valid.ctypes.data_as(u8p), ctypes.byref(st)), "zkmi_groth16_verify_each")
@@ -722,7 +711,7 @@ def proofs_decode(ctx: Context, fmt: int, raws):
     of a non-ok proof are zero."""
     buf, nb = _encoded(fmt, raws)
     a, b, c = np.zeros((nb, 8), np.uint64), np.zeros((nb, 16), np.uint64), np.zeros((nb, 8), np.uint64)
-    status = np.zeros(max(nb, 1), np.uint8)
+    status = _outbuf(nb, dtype=np.uint8)
     check(lib().zkmi_proofs_decode(ctx.h, fmt, buf.ctypes.data_as(u8p), nb, _p64(a), _p64(b), _p64(c),
                                    status.ctypes.data_as(u8p)), "zkmi_proofs_decode")
     return a, b, c, status[:nb]
@@ -757,7 +746,7 @@ def groth16_verify_many_encoded(ctx: Context, vk: VerifyingKey, fmt: int, raws, 
         if len(rho) != nb or any(not 0 <= int(v) < 1 << 128 for v in rho):
             raise ValueError("one 128-bit weight per proof")
         w = np.array([[int(v) & (2**64 - 1), int(v) >> 64] for v in rho], np.uint64).reshape(nb, 2)
-    valid, mal = np.zeros(max(nb, 1), np.uint8), np.zeros(max(nb, 1), np.uint8)
+    valid, mal = _outbuf(nb, dtype=np.uint8), _outbuf(nb, dtype=np.uint8)
     st = VerifyStatsStruct()
     check(lib().zkmi_groth16_verify_many_encoded(ctx.h, vk.h, fmt, nb, buf.ctypes.data_as(u8p), _p64(ins),
                                                  None if w is None else _p64(w), valid.ctypes.data_as(u8p),
@@ -771,7 +760,7 @@ def groth16_verify_each_encoded(ctx: Context, vk: VerifyingKey, fmt: int, raws, 
     proofs; arguments and results as groth16_verify_many_encoded's."""
     buf, nb = _encoded(fmt, raws)
     ins = _input_array(vk, nb, inputs)
-    valid, mal = np.zeros(max(nb, 1), np.uint8), np.zeros(max(nb, 1), np.uint8)
+    valid, mal = _outbuf(nb, dtype=np.uint8), _outbuf(nb, dtype=np.uint8)
     st = VerifyStatsStruct()
     check(lib().zkmi_groth16_verify_each_encoded(ctx.h, vk.h, fmt, nb, buf.ctypes.data_as(u8p), _p64(ins),
                                                  valid.ctypes.data_as(u8p), mal.ctypes.data_as(u8p),
@@ -779,28 +768,17 @@ def groth16_verify_each_encoded(ctx: Context, vk: VerifyingKey, fmt: int, raws, 
     return [bool(v) for v in valid[:nb]], [bool(v) for v in mal[:nb]], _stats(st)
 
 
-class R1CSDevice:
+class R1CSDevice(_Handle):
     """Circuit matrices resident in HBM (zkmi_r1cs_create)."""
+    _destroy = "zkmi_r1cs_destroy"
 
     def __init__(self, ctx: Context, cs):
         self.ctx = ctx
         st, keep = r1cs_struct(cs)
-        self.h = vp()
-        ctx._track(self)
+        self._open(ctx)
         check(lib().zkmi_r1cs_create(ctx.h, ctypes.byref(st), ctypes.byref(self.h)), "zkmi_r1cs_create")
         self.num_variables = cs.num_instance + cs.num_witness
         del keep
-
-    def close(self):
-        if self.h:
-            lib().zkmi_r1cs_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 @dataclass
@@ -920,57 +898,50 @@ def _fe_words(vals, width: int = 1) -> np.ndarray:
     return np.frombuffer(raw, np.uint64).reshape(-1, 4 * width).copy()
 
 
-class PoseidonHasher:
+def _hash_many(self, fn_name: str, tuples, arity: int | None) -> np.ndarray:
+    """hash_many of a resident hasher (fn_name: its entry point): one hash per
+    tuple, as an (n, 4) u64 array.  tuples: an (n, 4 * arity) u64 array (arity
+    given), or equally long sequences of ints / 32-byte strings."""
+    if arity is None:
+        tuples = [tuple(t) for t in tuples]
+        arity = len(tuples[0]) if tuples else 1
+        if any(len(t) != arity for t in tuples):
+            raise ValueError("hash_many: tuples of one length")
+        tuples = [x for t in tuples for x in t]
+    ins = _fe_words(tuples, arity)
+    n = ins.shape[0]
+    out = _outbuf(n, 4)
+    check(getattr(lib(), fn_name)(self.ctx.h, self.h, n, arity, _p64(ins), _p64(out)), fn_name)
+    return out[:n]
+
+
+class PoseidonHasher(_Handle):
     """Resident constants of one Poseidon parameter set (zkmi_poseidon_create):
     width 3, x^5, `params` as l2block.poseidon_params gives them."""
+    _destroy = "zkmi_poseidon_destroy"
 
     def __init__(self, ctx: Context, params):
         if params["rate"] != 2 or params["capacity"] != 1 or params["alpha"] != 5:
             raise ValueError("PoseidonHasher: rate 2, capacity 1, x^5 only")
         self.ctx, self.params = ctx, params
-        self.h = vp()
-        ctx._track(self)
+        self._open(ctx)
         table = _fe_words([int(c) for row in params["ark"] for c in row] + [int(c) for row in params["mds"] for c in row])
         check(lib().zkmi_poseidon_create(ctx.h, params["full"], params["partial"], _p64(table), ctypes.byref(self.h)),
               "zkmi_poseidon_create")
 
     def hash_many(self, tuples, arity: int | None = None) -> np.ndarray:
-        """zkmi_poseidon_hash_many: one sponge hash per tuple, as an (n, 4) u64
-        array.  tuples: an (n, 4 * arity) u64 array (arity given), or equally
-        long sequences of ints / 32-byte strings."""
-        if arity is None:
-            tuples = [tuple(t) for t in tuples]
-            arity = len(tuples[0]) if tuples else 1
-            if any(len(t) != arity for t in tuples):
-                raise ValueError("hash_many: tuples of one length")
-            tuples = [x for t in tuples for x in t]
-        ins = _fe_words(tuples, arity)
-        n = ins.shape[0]
-        out = np.zeros((max(n, 1), 4), np.uint64)
-        check(lib().zkmi_poseidon_hash_many(self.ctx.h, self.h, n, arity, _p64(ins), _p64(out)),
-              "zkmi_poseidon_hash_many")
-        return out[:n]
-
-    def close(self):
-        if self.h:
-            lib().zkmi_poseidon_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        """zkmi_poseidon_hash_many: one sponge hash per tuple (see _hash_many)."""
+        return _hash_many(self, "zkmi_poseidon_hash_many", tuples, arity)
 
 
-class NoteTreeDevice:
+class NoteTreeDevice(_Handle):
     """An append-only Merkle tree over a PoseidonHasher, resident in HBM
     (zkmi_note_tree_create).  Arrays are (n, 4) u64 canonical words."""
+    _destroy = "zkmi_note_tree_destroy"
 
     def __init__(self, ctx: Context, hasher: PoseidonHasher, depth: int, capacity: int, empty_leaf):
         self.ctx, self.hasher, self.depth, self.capacity = ctx, hasher, depth, capacity
-        self.h = vp()
-        ctx._track(self)
+        self._open(ctx)
         check(lib().zkmi_note_tree_create(ctx.h, hasher.h, depth, capacity, _p64(_fe_words([empty_leaf])),
                                           ctypes.byref(self.h)), "zkmi_note_tree_create")
 
@@ -985,7 +956,7 @@ class NoteTreeDevice:
         lv = _fe_words(leaves)
         n = lv.shape[0]
         first = ctypes.c_uint64(0)
-        roots = np.zeros((max(n, 1), 4), np.uint64) if want_roots else None
+        roots = _outbuf(n, 4) if want_roots else None
         check(lib().zkmi_note_tree_append(self.ctx.h, self.h, n, _p64(lv), ctypes.byref(first),
                                           None if roots is None else _p64(roots)), "zkmi_note_tree_append")
         return int(first.value), None if roots is None else roots[:n]
@@ -997,75 +968,41 @@ class NoteTreeDevice:
 
     def paths(self, positions) -> np.ndarray:
         """-> (n, depth, 4) siblings, the leaf level first"""
-        pos = np.ascontiguousarray(np.asarray(list(positions), np.uint64))
-        out = np.zeros((max(pos.size, 1), self.depth, 4), np.uint64)
+        pos = _positions(positions)
+        out = _outbuf(pos.size, self.depth, 4)
         check(lib().zkmi_note_tree_paths(self.ctx.h, self.h, pos.size, _p64(pos), _p64(out)), "zkmi_note_tree_paths")
         return out[:pos.size]
 
     def leaves(self, first: int, n: int) -> np.ndarray:
-        out = np.zeros((max(n, 1), 4), np.uint64)
+        out = _outbuf(n, 4)
         check(lib().zkmi_note_tree_leaves(self.ctx.h, self.h, first, n, _p64(out)), "zkmi_note_tree_leaves")
         return out[:n]
 
-    def close(self):
-        if self.h:
-            lib().zkmi_note_tree_destroy(self.h)
-            self.h = vp()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class MimcHasher:
+class MimcHasher(_Handle):
     """Resident MiMC round constants (zkmi_mimc_create): the zelana_batch
     circuit's hash_1 .. hash_4, one lane per hash."""
+    _destroy = "zkmi_mimc_destroy"
 
     def __init__(self, ctx: Context):
         self.ctx = ctx
-        self.h = vp()
-        ctx._track(self)
+        self._open(ctx)
         check(lib().zkmi_mimc_create(ctx.h, ctypes.byref(self.h)), "zkmi_mimc_create")
 
     def hash_many(self, tuples, arity: int | None = None) -> np.ndarray:
-        """zkmi_mimc_hash_many: hash_arity of every tuple, as an (n, 4) u64
-        array.  tuples: an (n, 4 * arity) u64 array (arity given), or equally
-        long sequences of ints / 32-byte strings."""
-        if arity is None:
-            tuples = [tuple(t) for t in tuples]
-            arity = len(tuples[0]) if tuples else 1
-            if any(len(t) != arity for t in tuples):
-                raise ValueError("hash_many: tuples of one length")
-            tuples = [x for t in tuples for x in t]
-        ins = _fe_words(tuples, arity)
-        n = ins.shape[0]
-        out = np.zeros((max(n, 1), 4), np.uint64)
-        check(lib().zkmi_mimc_hash_many(self.ctx.h, self.h, n, arity, _p64(ins), _p64(out)), "zkmi_mimc_hash_many")
-        return out[:n]
-
-    def close(self):
-        if self.h:
-            lib().zkmi_mimc_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        """zkmi_mimc_hash_many: hash_arity of every tuple (see _hash_many)."""
+        return _hash_many(self, "zkmi_mimc_hash_many", tuples, arity)
 
 
-class AccountTreeDevice:
+class AccountTreeDevice(_Handle):
     """The sparse MiMC account tree, resident in HBM (zkmi_account_tree_create):
     any position below 2^depth, a node store of max_nodes slots.  Arrays are
     (n, 4) u64 canonical words."""
+    _destroy = "zkmi_account_tree_destroy"
 
     def __init__(self, ctx: Context, hasher: MimcHasher, depth: int, max_nodes: int):
         self.ctx, self.hasher, self.depth, self.max_nodes = ctx, hasher, depth, max_nodes
-        self.h = vp()
-        ctx._track(self)
+        self._open(ctx)
         check(lib().zkmi_account_tree_create(ctx.h, hasher.h, depth, max_nodes, ctypes.byref(self.h)),
               "zkmi_account_tree_create")
 
@@ -1078,13 +1015,13 @@ class AccountTreeDevice:
     def apply(self, positions, leaves):
         """K ordered leaf writes -> ((K, depth, 4) siblings as write k sees
         them, (K, 4) replaced leaves, (K, 4) roots after each write)"""
-        pos = np.ascontiguousarray(np.asarray(list(positions), np.uint64))
+        pos = _positions(positions)
         lv = _fe_words(leaves)
         if lv.shape[0] != pos.size:
             raise ValueError("apply: one leaf per position")
         k = pos.size
-        sib = np.zeros((max(k, 1), self.depth, 4), np.uint64)
-        old, roots = np.zeros((max(k, 1), 4), np.uint64), np.zeros((max(k, 1), 4), np.uint64)
+        sib = _outbuf(k, self.depth, 4)
+        old, roots = _outbuf(k, 4), _outbuf(k, 4)
         check(lib().zkmi_account_tree_apply(self.ctx.h, self.h, k, _p64(pos), _p64(lv), _p64(sib), _p64(old),
                                             _p64(roots)), "zkmi_account_tree_apply")
         return sib[:k], old[:k], roots[:k]
@@ -1096,29 +1033,18 @@ class AccountTreeDevice:
 
     def paths(self, positions) -> np.ndarray:
         """-> (n, depth, 4) siblings against the current state, the leaf level first"""
-        pos = np.ascontiguousarray(np.asarray(list(positions), np.uint64))
-        out = np.zeros((max(pos.size, 1), self.depth, 4), np.uint64)
+        pos = _positions(positions)
+        out = _outbuf(pos.size, self.depth, 4)
         check(lib().zkmi_account_tree_paths(self.ctx.h, self.h, pos.size, _p64(pos), _p64(out)),
               "zkmi_account_tree_paths")
         return out[:pos.size]
 
     def leaves(self, positions) -> np.ndarray:
-        pos = np.ascontiguousarray(np.asarray(list(positions), np.uint64))
-        out = np.zeros((max(pos.size, 1), 4), np.uint64)
+        pos = _positions(positions)
+        out = _outbuf(pos.size, 4)
         check(lib().zkmi_account_tree_leaves(self.ctx.h, self.h, pos.size, _p64(pos), _p64(out)),
               "zkmi_account_tree_leaves")
         return out[:pos.size]
-
-    def close(self):
-        if self.h:
-            lib().zkmi_account_tree_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _key_bytes(keys) -> np.ndarray:
@@ -1138,15 +1064,15 @@ def _key_bytes(keys) -> np.ndarray:
 NF_ACCEPTED, NF_SKIPPED, NF_SPENT_STORED, NF_SPENT_IN_CALL, NF_DUP_IN_TX = 0, 1, 2, 3, 4  # ZKMI_NF_*
 
 
-class NullifierSetDevice:
+class NullifierSetDevice(_Handle):
     """The spent-nullifier set, resident in HBM (zkmi_nullifier_set_create): at
     most `capacity` keys of 32 raw bytes, compared bytewise, kept in insertion
     order."""
+    _destroy = "zkmi_nullifier_set_destroy"
 
     def __init__(self, ctx: Context, capacity: int):
         self.ctx, self.capacity = ctx, capacity
-        self.h = vp()
-        ctx._track(self)
+        self._open(ctx)
         check(lib().zkmi_nullifier_set_create(ctx.h, capacity, ctypes.byref(self.h)), "zkmi_nullifier_set_create")
 
     def info(self):
@@ -1163,7 +1089,7 @@ class NullifierSetDevice:
         """[bool per key]"""
         kb = _key_bytes(keys)
         n = kb.shape[0]
-        out = np.zeros(max(n, 1), np.uint8)
+        out = _outbuf(n, dtype=np.uint8)
         check(lib().zkmi_nullifier_set_contains(self.ctx.h, self.h, n, kb.ctypes.data_as(u8p), out.ctypes.data_as(u8p)),
               "zkmi_nullifier_set_contains")
         return out[:n].astype(bool).tolist()
@@ -1181,7 +1107,7 @@ class NullifierSetDevice:
             el = np.ascontiguousarray([1 if e else 0 for e in eligible], np.uint8)
             if el.size != ntx:
                 raise ValueError("spend: one eligible flag per transfer")
-        verdict, detail = np.zeros(max(ntx, 1), np.uint32), np.zeros(max(ntx, 1), np.uint32)
+        verdict, detail = _outbuf(ntx, dtype=np.uint32), _outbuf(ntx, dtype=np.uint32)
         rounds = ctypes.c_uint32(0)
         check(lib().zkmi_nullifier_set_spend(self.ctx.h, self.h, ntx, per_tx, kb.ctypes.data_as(u8p),
                                              None if el is None else el.ctypes.data_as(u8p),
@@ -1196,21 +1122,10 @@ class NullifierSetDevice:
 
     def log(self, first: int, n: int) -> list:
         """the keys [first, first + n) in insertion order, as 32-byte strings"""
-        out = np.zeros((max(n, 1), 32), np.uint8)
+        out = _outbuf(n, 32, dtype=np.uint8)
         check(lib().zkmi_nullifier_set_log(self.ctx.h, self.h, first, n, out.ctypes.data_as(u8p)),
               "zkmi_nullifier_set_log")
         return [out[i].tobytes() for i in range(n)]
-
-    def close(self):
-        if self.h:
-            lib().zkmi_nullifier_set_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 SCAN_NOT_MINE, SCAN_MALFORMED, SCAN_WRONG_COMMITMENT, SCAN_HIT = 0, 1, 2, 3  # ZKMI_SCAN_*
@@ -1227,16 +1142,16 @@ class ScannedNote:
     memo: bytes
 
 
-class NoteStoreDevice:
+class NoteStoreDevice(_Handle):
     """The encrypted notes of a pool, resident in HBM (zkmi_note_store_create):
     at most `capacity` notes whose ciphertexts, tag included, are at most
     max_ct bytes; append-only.  hashers: mimc= a MimcHasher for COMMIT_MIMC
     scans, poseidon= a PoseidonHasher for COMMIT_POSEIDON ones."""
+    _destroy = "zkmi_note_store_destroy"
 
     def __init__(self, ctx: Context, capacity: int, max_ct: int = 570, mimc=None, poseidon=None):
         self.ctx, self.capacity, self.max_ct, self.mimc, self.poseidon = ctx, capacity, max_ct, mimc, poseidon
-        self.h = vp()
-        ctx._track(self)
+        self._open(ctx)
         check(lib().zkmi_note_store_create(ctx.h, capacity, max_ct, ctypes.byref(self.h)), "zkmi_note_store_create")
 
     def info(self):
@@ -1331,14 +1246,3 @@ class NoteStoreDevice:
                     for j in range(int(counts[k]))]
             out.append((hits, int(to[k]), [int(v) for v in stats[k]]))
         return out
-
-    def close(self):
-        if self.h:
-            lib().zkmi_note_store_destroy(self.h)
-            self.h = vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
