@@ -897,6 +897,37 @@ int zkmi_note_scan(zkmi_ctx* ctx, const zkmi_note_store* store, const zkmi_mimc*
                    uint32_t* positions, uint64_t* values, uint8_t* randomness, uint8_t* commitments,
                    uint32_t* memo_lens, uint8_t* memos);
 
+/* ------------------------------------------------------ Ed25519 verification
+ * The signatures of the sequencer's transparent path (transfers and
+ * withdrawals), verified in batches, one GPU lane per signature (DESIGN.md
+ * section 2.16).  The semantics are ed25519-dalek 2.2.0 `verify` (not
+ * verify_strict) over curve25519-dalek 4.1.3, which the reference calls:
+ *   - the public key A decompresses by dalek's rules: bit 255 is the sign of
+ *     x, the low 255 bits are y and need not be below p (they are reduced),
+ *     x = 0 with the sign bit set is accepted; only a y on no point fails;
+ *   - s >= L is refused;
+ *   - k = SHA-512(R || A as given || M) mod L, and the canonical 32 bytes of
+ *     [s]B + [k](-A) are compared with R: no cofactor, a small-order A is
+ *     accepted, and a non-canonical R fails because its bytes differ.
+ * When several reasons apply, BAD_PUBKEY comes before BAD_S: the reference
+ * parses the key first.  The time of a call does not depend on the verdicts. */
+#define ZKMI_SIG_OK          0
+#define ZKMI_SIG_BAD_PUBKEY  1  /* A does not decompress */
+#define ZKMI_SIG_BAD_S       2  /* s >= L */
+#define ZKMI_SIG_MISMATCH    3  /* the equation does not hold (a non-canonical R included) */
+/* pubkeys: n x 32 bytes; sigs: n x 64 bytes (R, then s); msgs: the messages
+ * back to back, of any lengths, 0 included; msg_offsets: n + 1 ascending byte
+ * offsets into msgs, [0] = 0, message i = [msg_offsets[i], msg_offsets[i + 1]);
+ * verdicts: n bytes, a ZKMI_SIG_* each.  n = 0 does nothing and launches
+ * nothing.  ZKMI_EINVAL for a null argument, msg_offsets[0] != 0, offsets that
+ * descend, or more than 2^26 signatures; verdicts is then not written.  The
+ * call keeps 137 bytes a signature plus the message bytes of workspace on the
+ * context (keys, signatures, offsets, k, verdicts), and 2560 bytes a signature
+ * for the tables of -A of at most 2^18 signatures at a time (640 MiB at most),
+ * beside 2560 bytes for the table of B, made on the context's first call. */
+int zkmi_ed25519_verify_many(zkmi_ctx* ctx, size_t n, const uint8_t* pubkeys, const uint8_t* sigs, const uint8_t* msgs,
+                             const uint64_t* msg_offsets, uint8_t* verdicts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ Deviations from the reference, on purpose:
 zbatch.SparseTree / synthetic_batch / mimc_hash stay what they are: the oracle."""
 from __future__ import annotations
 
-from . import gpu
+from . import gpu, tx_auth
 from .r1cs import R
 
 
@@ -81,7 +81,29 @@ class DeviceAccountState:
         return self.insert_many([(account_id, balance, nonce)])
 
     # ----------------------------------------------------------------- batches
-    def batches(self, batches, max_transfers: int = 8, max_withdrawals: int = 4):
+    @staticmethod
+    def _authorise(batches, verifier):
+        """the signed entries of all batches through one verify_signed; a
+        refused one raises ValueError.  -> the batches with tuples throughout"""
+        signed = [(b["batch_id"], kind, i, e) for b in batches for kind in ("transfers", "withdrawals")
+                  for i, e in enumerate(b.get(kind, [])) if isinstance(e, (tx_auth.SignedTransfer, tx_auth.SignedWithdrawal))]
+        if not signed:
+            return batches
+        if verifier is None:
+            raise ValueError("signed transfers and withdrawals need a verifier")
+        for bid, kind, i, e in signed:
+            if isinstance(e, tx_auth.SignedTransfer) != (kind == "transfers"):
+                raise ValueError(f"batch {bid}: {kind}[{i}] is a {type(e).__name__}")
+        reasons, _ = tx_auth.verify_signed(verifier, [e for *_, e in signed])
+        for (bid, kind, i, _), reason in zip(signed, reasons):
+            if reason != tx_auth.OK:
+                raise ValueError(f"batch {bid}: {kind}[{i}] refused: {reason}")
+        as_tuple = lambda e: (tx_auth.transfer_tuple(e) if isinstance(e, tx_auth.SignedTransfer) else
+                              tx_auth.withdrawal_tuple(e) if isinstance(e, tx_auth.SignedWithdrawal) else e)
+        return [{**b, "transfers": [as_tuple(e) for e in b.get("transfers", [])],
+                 "withdrawals": [as_tuple(e) for e in b.get("withdrawals", [])]} for b in batches]
+
+    def batches(self, batches, max_transfers: int = 8, max_withdrawals: int = 4, verifier=None):
         """batches: [{"batch_id": int, "transfers": [(sender id, receiver id,
         amount, signature)], "withdrawals": [(sender id, l1_recipient, amount,
         signature)]}], applied in order, the transfers of a batch before its
@@ -90,8 +112,22 @@ class DeviceAccountState:
         them.  A batch with more transfers than max_transfers or more
         withdrawals than max_withdrawals (the circuit's slot counts) raises
         ValueError, an unknown id KeyError; both before anything changes.
-        Amounts, signatures and ids may be any integer type."""
+        Amounts, signatures and ids may be any integer type.
+
+        verifier (a gpu.Ed25519Verifier, or anything with its verify_many):
+        an entry may then be a tx_auth.SignedTransfer or SignedWithdrawal in
+        place of a tuple.  The signatures of all batches are checked in one
+        pass (tx_auth.verify_signed: the readable message first, the legacy
+        one for the failures) before anything changes, and a refused one
+        raises ValueError naming the batch, the index and the reason.  The
+        circuit's `signature` input then carries the first 31 bytes of the
+        signature as a big-endian integer (tx_auth.signature_field): a
+        pass-through value the circuit does not constrain; the check that
+        counts is the one made here.  Nonces and balances are not judged here,
+        with or without a verifier.  Without a verifier nothing differs from
+        before, and a signed entry raises ValueError."""
         depth = self.depth
+        batches = self._authorise(list(batches), verifier)
         norm = []
         for b in batches:
             ts = [(bytes(s), bytes(r), int(amount), int(sig)) for s, r, amount, sig in b.get("transfers", [])]

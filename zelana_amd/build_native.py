@@ -23,6 +23,7 @@ SHARD_TEST = os.path.join(HERE, "test_sharded_msm")    # 2-rank sharded MSM over
 FF_PROBE = os.path.join(HERE, "libzkmi_ffprobe.so")    # ff.h / ec.h op table on the device (tests/device/), tests only
 FF_HOST = os.path.join(HERE, "libff_host.so")          # the same table on the CPU (tests/native/ff_host_shim.cpp)
 NC_PROBE = os.path.join(HERE, "libzkmi_ncprobe.so")    # note_crypt.h op table on the device (tests/device/), tests only
+ED_PROBE = os.path.join(HERE, "libzkmi_edprobe.so")    # ed25519.h op table on the device (tests/device/), tests only
 ROCM_LIB = "/opt/rocm/lib"
 ARCH = os.environ.get("ZKMI_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -78,6 +79,7 @@ def build(verbose: bool = False) -> str:
     _build_host(verbose)
     _build_ff_ops(verbose)
     _build_nc_probe(verbose)
+    _build_ed_probe(verbose)
     if verbose:
         print("built", LIB)
     return LIB
@@ -141,6 +143,24 @@ def _build_nc_probe(verbose: bool):
         raise RuntimeError("note_crypt probe build failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
     if verbose:
         print("built", NC_PROBE)
+
+
+def _build_ed_probe(verbose: bool):
+    """libzkmi_edprobe.so: the op table over ed25519.h alone
+    (tests/device/ed25519_ops.h) on the device.  It does not link libzkmi.so,
+    and only the tests load it; the same table runs on the CPU as a stand-alone
+    program the tests build themselves (tests/host/ed25519_check.cpp)."""
+    dev = os.path.join(HERE, "..", "tests", "device")
+    src = os.path.join(dev, "ed25519_probe.hip")
+    deps = [src, os.path.join(dev, "ed25519_ops.h"), os.path.join(CSRC, "ed25519.h"), os.path.join(CSRC, "note_crypt.h")]
+    if os.path.exists(ED_PROBE) and all(os.path.getmtime(d) <= os.path.getmtime(ED_PROBE) for d in deps):
+        return
+    cmd = [HIPCC] + HIP_FLAGS + ["-shared", "-L" + ROCM_LIB, "-Wl,-rpath," + ROCM_LIB, "-o", ED_PROBE, src]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("ed25519 probe build failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
+    if verbose:
+        print("built", ED_PROBE)
 
 
 if __name__ == "__main__":

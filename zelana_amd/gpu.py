@@ -1246,3 +1246,46 @@ class NoteStoreDevice(_Handle):
                     for j in range(int(counts[k]))]
             out.append((hits, int(to[k]), [int(v) for v in stats[k]]))
         return out
+
+
+SIG_OK, SIG_BAD_PUBKEY, SIG_BAD_S, SIG_MISMATCH = 0, 1, 2, 3  # ZKMI_SIG_*
+
+
+class Ed25519Verifier:
+    """Batched Ed25519 verification on the device (zkmi_ed25519_verify_many,
+    DESIGN.md §2.16): ed25519-dalek 2.2.0 `verify` semantics, one lane per
+    signature.  It holds no device state of its own: the workspace and the
+    table of the base point live on the context."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+
+    def verify_many(self, pubkeys, msgs, sigs) -> np.ndarray:
+        """pubkeys: n x 32 bytes, msgs: n byte strings of any length, sigs:
+        n x 64 bytes -> a uint8 array of n SIG_* verdicts"""
+        pubkeys, msgs, sigs = [bytes(p) for p in pubkeys], [bytes(m) for m in msgs], [bytes(s) for s in sigs]
+        n = len(pubkeys)
+        if len(msgs) != n or len(sigs) != n:
+            raise ValueError("verify_many: one message and one signature per public key")
+        if any(len(p) != 32 for p in pubkeys) or any(len(s) != 64 for s in sigs):
+            raise ValueError("verify_many: 32-byte public keys and 64-byte signatures")
+        off = np.zeros(n + 1, np.uint64)
+        np.cumsum([len(m) for m in msgs], out=off[1:])
+        return self.verify_arrays(np.frombuffer(b"".join(pubkeys), np.uint8), np.frombuffer(b"".join(sigs), np.uint8),
+                                  np.frombuffer(b"".join(msgs), np.uint8), off)
+
+    def verify_arrays(self, pubkeys, sigs, msgs, offsets) -> np.ndarray:
+        """verify_many over ready arrays: u8 (n x 32), u8 (n x 64), u8 (the
+        messages back to back), u64 (n + 1 offsets, [0] = 0, ascending)"""
+        pk, sg, ms = (np.ascontiguousarray(a, np.uint8).reshape(-1) for a in (pubkeys, sigs, msgs))
+        off = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+        n = off.size - 1
+        if n < 0 or pk.size != 32 * n or sg.size != 64 * n or ms.size < int(off[-1]):
+            raise ValueError("verify_arrays: array sizes do not agree")
+        out = np.zeros(max(n, 1), np.uint8)
+        if ms.size == 0:
+            ms = np.zeros(1, np.uint8)
+        check(lib().zkmi_ed25519_verify_many(self.ctx.h, n, pk.ctypes.data_as(u8p), sg.ctypes.data_as(u8p),
+                                             ms.ctypes.data_as(u8p), _p64(off), out.ctypes.data_as(u8p)),
+              "zkmi_ed25519_verify_many")
+        return out[:n]
