@@ -21,6 +21,7 @@ HOST_LIB = os.path.join(HERE, "libzelana_prover.so")   # C++ mirror of the refer
 HOST_TEST = os.path.join(HERE, "test_batch_prover")    # its C++ unit tests (tests/host/test_batch_prover.cpp)
 SHARD_TEST = os.path.join(HERE, "test_sharded_msm")    # 2-rank sharded MSM over zkmi.h alone (tests/host/)
 FF_PROBE = os.path.join(HERE, "libzkmi_ffprobe.so")    # ff.h / ec.h op table on the device (tests/device/), tests only
+FF_PROBE_1MAD = os.path.join(HERE, "libzkmi_ffprobe_1mad.so")  # the same probe, -DZK_MAD_BLOCKS=0 (one mad an asm statement)
 FF_HOST = os.path.join(HERE, "libff_host.so")          # the same table on the CPU (tests/native/ff_host_shim.cpp)
 NC_PROBE = os.path.join(HERE, "libzkmi_ncprobe.so")    # note_crypt.h op table on the device (tests/device/), tests only
 ED_PROBE = os.path.join(HERE, "libzkmi_edprobe.so")    # ed25519.h op table on the device (tests/device/), tests only
@@ -109,13 +110,16 @@ def _build_host(verbose: bool):
 
 def _build_ff_ops(verbose: bool):
     """The per-op test libraries over ff.h / ec.h alone (tests/device/ff_ops.h):
-    libzkmi_ffprobe.so (hipcc, device) and libff_host.so (g++, CPU).  Neither
-    links libzkmi.so, and only the tests load them."""
+    libzkmi_ffprobe.so (hipcc, device), libzkmi_ffprobe_1mad.so (the same with
+    ff.h's one-mad asm statements instead of its mad blocks, for
+    tests/test_gpu_mad_blocks.py) and libff_host.so (g++, CPU).  None links
+    libzkmi.so, and only the tests load them."""
     tests = os.path.join(HERE, "..", "tests")
     table = os.path.join(tests, "device", "ff_ops.h")
     hdrs = [table, os.path.join(CSRC, "ff.h"), os.path.join(CSRC, "ec.h")]
-    for out, src, cmd in ((FF_PROBE, os.path.join(tests, "device", "ff_probe.hip"),
-                           [HIPCC] + HIP_FLAGS + ["-shared", "-L" + ROCM_LIB, "-Wl,-rpath," + ROCM_LIB]),
+    probe = [HIPCC] + HIP_FLAGS + ["-shared", "-L" + ROCM_LIB, "-Wl,-rpath," + ROCM_LIB]
+    for out, src, cmd in ((FF_PROBE, os.path.join(tests, "device", "ff_probe.hip"), probe),
+                          (FF_PROBE_1MAD, os.path.join(tests, "device", "ff_probe.hip"), probe + ["-DZK_MAD_BLOCKS=0"]),
                           (FF_HOST, os.path.join(tests, "native", "ff_host_shim.cpp"), ["g++"] + CXX_FLAGS + ["-shared"])):
         if os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in [src] + hdrs):
             continue

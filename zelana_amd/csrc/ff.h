@@ -38,6 +38,7 @@ struct Fe {
 // Base field q (G1/G2 coordinates)
 struct FqP {
   static constexpr bool ASM = true;
+  static constexpr bool BLK = true;  // the asm products emit their mads as blocks (ZK_MAD_BLOCKS below)
   static constexpr uint32_t P[NL] = {0x187cfd47u, 0x010460b6u, 0x1c72a34fu, 0x02d522d0u, 0x1585d978u,
                                      0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu};
   static constexpr uint32_t P2[NL] = {0x10f9fa8eu, 0x0208c16du, 0x18e5469eu, 0x05aa45a1u, 0x0b0bb2f0u,
@@ -72,6 +73,10 @@ struct FqP {
 // Scalar field r (NTT domain)
 struct FrP {
   static constexpr bool ASM = true;  // (compiler-scheduled products: 2^24 NTT+INTT 4.41 -> 5.30 ms)
+  // one mad an asm statement: with the blocks k_ntt_group loses three quarters
+  // of its nops (2,160 -> 425) but the 2^24 NTT+INTT goes 3.77 -> 3.96 ms
+  // (profiles/mad_blocks/)
+  static constexpr bool BLK = false;
   static constexpr uint32_t P[NL] = {0x10000001u, 0x1f0fac9fu, 0x0e5c2450u, 0x07d090f3u, 0x1585d283u,
                                      0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu};
   static constexpr uint32_t P2[NL] = {0x00000002u, 0x1e1f593fu, 0x1cb848a1u, 0x0fa121e6u, 0x0b0ba506u,
@@ -172,6 +177,85 @@ ZK_HD void macs(uint64_t& acc, uint32_t a, uint32_t b) { acc += (uint64_t)a * b;
 ZK_HD void mac1(uint64_t& acc, uint32_t d) { acc += d; }
 #endif
 
+// ZK_MAD_BLOCKS (default 1): the P::ASM products of a field with P::BLK (Fq)
+// emit a column's mads as blocks, K dependent v_mad_u64_u32 in ONE asm
+// statement.  The hazard recognizer pads the first reader of an asm
+// statement's 64-bit VGPR result with an s_nop 0; with one mad a statement
+// that is nearly every mad of a column (~160 a product), with blocks one pad a
+// block (~40 a product).  Inside a block the mads follow each other as plain
+// C's do.  2^20 G1 table MSM, 2 lanes: 884 -> 910 Mpt/s (profiles/mad_blocks/).
+// -DZK_MAD_BLOCKS=0 keeps the one-mad statements (A/B,
+// tests/test_gpu_mad_blocks.py).
+#ifndef ZK_MAD_BLOCKS
+#define ZK_MAD_BLOCKS 1
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_NO_ASM_MAD) && ZK_MAD_BLOCKS
+#define ZK_BLOCKS_ON 1
+// col_ab<K>: acc += a[0] b[0] + a[1] b[1] + .. + a[K-1] b[K-1], a column's
+// products gathered by the caller (the gathers rename registers, they move
+// nothing).  col_mp<K>: the same with the second factor uniform (modulus
+// limbs: "s" operands, gfx9 VOP3 takes no literal).  The carry-out pair is
+// early-clobber: the later mads of a block read their SGPR operands after the
+// first has written it.  An asm statement takes 30 operands, so a block holds
+// at most 9 products (2 + 2 x 9).
+#define ZK_M(x, y) "v_mad_u64_u32 %0, %1, %" #x ", %" #y ", %0\n\t"
+#define ZK_MADS1 ZK_M(2, 3)
+#define ZK_MADS2 ZK_MADS1 ZK_M(4, 5)
+#define ZK_MADS3 ZK_MADS2 ZK_M(6, 7)
+#define ZK_MADS4 ZK_MADS3 ZK_M(8, 9)
+#define ZK_MADS5 ZK_MADS4 ZK_M(10, 11)
+#define ZK_MADS6 ZK_MADS5 ZK_M(12, 13)
+#define ZK_MADS7 ZK_MADS6 ZK_M(14, 15)
+#define ZK_MADS8 ZK_MADS7 ZK_M(16, 17)
+#define ZK_MADS9 ZK_MADS8 ZK_M(18, 19)
+#define ZK_OPS1(c) "v"(a[0]), c(b[0])
+#define ZK_OPS2(c) ZK_OPS1(c), "v"(a[1]), c(b[1])
+#define ZK_OPS3(c) ZK_OPS2(c), "v"(a[2]), c(b[2])
+#define ZK_OPS4(c) ZK_OPS3(c), "v"(a[3]), c(b[3])
+#define ZK_OPS5(c) ZK_OPS4(c), "v"(a[4]), c(b[4])
+#define ZK_OPS6(c) ZK_OPS5(c), "v"(a[5]), c(b[5])
+#define ZK_OPS7(c) ZK_OPS6(c), "v"(a[6]), c(b[6])
+#define ZK_OPS8(c) ZK_OPS7(c), "v"(a[7]), c(b[7])
+#define ZK_OPS9(c) ZK_OPS8(c), "v"(a[8]), c(b[8])
+template <int K>
+__device__ __forceinline__ void col_ab(uint64_t& acc, const uint32_t* a, const uint32_t* b);
+template <int K>
+__device__ __forceinline__ void col_mp(uint64_t& acc, const uint32_t* a, const uint32_t* b);
+#define ZK_COL(K)                                                                                    \
+  template <>                                                                                        \
+  __device__ __forceinline__ void col_ab<K>(uint64_t & acc, const uint32_t* a, const uint32_t* b) {  \
+    uint64_t cy;                                                                                     \
+    asm(ZK_MADS##K : "+v"(acc), "=&s"(cy) : ZK_OPS##K("v"));                                         \
+  }                                                                                                  \
+  template <>                                                                                        \
+  __device__ __forceinline__ void col_mp<K>(uint64_t & acc, const uint32_t* a, const uint32_t* b) {  \
+    uint64_t cy;                                                                                     \
+    asm(ZK_MADS##K : "+v"(acc), "=&s"(cy) : ZK_OPS##K("s"));                                         \
+  }
+ZK_COL(1) ZK_COL(2) ZK_COL(3) ZK_COL(4) ZK_COL(5) ZK_COL(6) ZK_COL(7) ZK_COL(8) ZK_COL(9)
+#undef ZK_COL
+// n products of a column, n a constant once the column loops are unrolled
+#define ZK_COLN(f)                                                                                     \
+  __device__ __forceinline__ void f##_n(uint64_t& acc, const uint32_t* a, const uint32_t* b, int n) {  \
+    switch (n) {                                                                                       \
+      case 1: f<1>(acc, a, b); break;                                                                  \
+      case 2: f<2>(acc, a, b); break;                                                                  \
+      case 3: f<3>(acc, a, b); break;                                                                  \
+      case 4: f<4>(acc, a, b); break;                                                                  \
+      case 5: f<5>(acc, a, b); break;                                                                  \
+      case 6: f<6>(acc, a, b); break;                                                                  \
+      case 7: f<7>(acc, a, b); break;                                                                  \
+      case 8: f<8>(acc, a, b); break;                                                                  \
+      case 9: f<9>(acc, a, b); break;                                                                  \
+      default: break;                                                                                  \
+    }                                                                                                  \
+  }
+ZK_COLN(col_ab) ZK_COLN(col_mp)
+#undef ZK_COLN
+#else
+#define ZK_BLOCKS_ON 0
+#endif
+
 // Product accumulation by field: P::ASM picks the one-chain inline-asm mads
 // (throughput kernels: G1, Fr) or plain C that the compiler may split into
 // parallel partial sums.  G2 (Fq2) code uses FqPn (ASM = false): at its 2
@@ -209,10 +293,131 @@ ZK_HD void pmac1(uint64_t& acc, uint32_t d) {
   acc += d;
 }
 
+#if ZK_BLOCKS_ON
+// The P::ASM products over the blocks.  Columns, the digit step and the
+// addends (mac1) are those of the plain routines below; inside a column the
+// a.b products come first as one block and the m.p products follow as another,
+// so a column sums the same terms and every result is bit-identical.
+// Column k of x * y, digits [lo, hi): acc += sum x[j] y[k - j]
+__device__ __forceinline__ void blk_ab(uint64_t& acc, const uint32_t* x, const uint32_t* y, int k, int lo, int hi) {
+  uint32_t s[NL], t[NL];
+#pragma unroll
+  for (int j = lo; j < hi; j++) {
+    s[j - lo] = x[j];
+    t[j - lo] = y[k - j];
+  }
+  col_ab_n(acc, s, t, hi - lo);
+}
+// acc += sum m[j] p[k - j], j in [lo, hi)
+template <class P>
+__device__ __forceinline__ void blk_mp(uint64_t& acc, const uint32_t* m, int k, int lo, int hi) {
+  uint32_t s[NL], t[NL];
+#pragma unroll
+  for (int j = lo; j < hi; j++) {
+    s[j - lo] = m[j];
+    t[j - lo] = P::P[k - j];
+  }
+  col_mp_n(acc, s, t, hi - lo);
+}
+// mul (ADD = false, d unused) and mul_add
+template <class P, bool ADD>
+__device__ __forceinline__ Fe mul_blk(const Fe& a, const Fe& b, const Fe& d) {
+  uint32_t m[NL];
+  Fe r;
+  uint64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    blk_ab(acc, a.v, b.v, k, 0, k + 1);
+    blk_mp<P>(acc, m, k, 0, k);
+    m[k] = ((uint32_t)acc * P::PINV) & LMASK;
+    macs(acc, m[k], P::P[0]);
+    acc >>= 29;
+  }
+#pragma unroll
+  for (int k = NL; k < 2 * NL - 1; k++) {
+    if (ADD) mac1(acc, d.v[k - NL]);
+    blk_ab(acc, a.v, b.v, k, k - (NL - 1), NL);
+    blk_mp<P>(acc, m, k, k - (NL - 1), NL);
+    r.v[k - NL] = (uint32_t)acc & LMASK;
+    acc >>= 29;
+  }
+  r.v[NL - 1] = ADD ? (uint32_t)acc + d.v[NL - 1] : (uint32_t)acc;
+  return r;
+}
+// sqr and sqr_add: a column's doubled off-diagonal products and its square in
+// one block
+template <class P, bool ADD>
+__device__ __forceinline__ Fe sqr_blk(const Fe& a, const Fe& d) {
+  uint32_t m[NL], dd[NL];
+  Fe r;
+#pragma unroll
+  for (int i = 0; i < NL; i++) dd[i] = a.v[i] << 1;
+  uint64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 2 * NL - 1; k++) {
+    const int lo = k < NL ? 0 : k - (NL - 1);
+    if (ADD && k >= NL) mac1(acc, d.v[k - NL]);
+    uint32_t s[NL], t[NL];
+    int n = 0;
+#pragma unroll
+    for (int j = lo; j < (k + 1) / 2; j++, n++) {
+      s[n] = dd[j];
+      t[n] = a.v[k - j];
+    }
+    if ((k & 1) == 0) {
+      s[n] = a.v[k / 2];
+      t[n] = a.v[k / 2];
+      n++;
+    }
+    col_ab_n(acc, s, t, n);
+    if (k < NL) {
+      blk_mp<P>(acc, m, k, 0, k);
+      m[k] = ((uint32_t)acc * P::PINV) & LMASK;
+      macs(acc, m[k], P::P[0]);
+    } else {
+      blk_mp<P>(acc, m, k, lo, NL);
+      r.v[k - NL] = (uint32_t)acc & LMASK;
+    }
+    acc >>= 29;
+  }
+  r.v[NL - 1] = ADD ? (uint32_t)acc + d.v[NL - 1] : (uint32_t)acc;
+  return r;
+}
+// mul2: three blocks a column (a.b, c.d, m.p)
+template <class P>
+__device__ __forceinline__ Fe mul2_blk(const Fe& a, const Fe& b, const Fe& c, const Fe& d) {
+  uint32_t m[NL];
+  Fe r;
+  uint64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    blk_ab(acc, a.v, b.v, k, 0, k + 1);
+    blk_ab(acc, c.v, d.v, k, 0, k + 1);
+    blk_mp<P>(acc, m, k, 0, k);
+    m[k] = ((uint32_t)acc * P::PINV) & LMASK;
+    macs(acc, m[k], P::P[0]);
+    acc >>= 29;
+  }
+#pragma unroll
+  for (int k = NL; k < 2 * NL - 1; k++) {
+    blk_ab(acc, a.v, b.v, k, k - (NL - 1), NL);
+    blk_ab(acc, c.v, d.v, k, k - (NL - 1), NL);
+    blk_mp<P>(acc, m, k, k - (NL - 1), NL);
+    r.v[k - NL] = (uint32_t)acc & LMASK;
+    acc >>= 29;
+  }
+  r.v[NL - 1] = (uint32_t)acc;
+  return r;
+}
+#endif
+
 // ------------------------------------------------------------ Montgomery mul
 // r = a*b*2^-261 mod p (lazy: result < 2p, normalised limbs).
 template <class P>
 ZK_HD Fe mul(const Fe& a, const Fe& b) {
+#if ZK_BLOCKS_ON
+  if constexpr (P::ASM && P::BLK) return mul_blk<P, false>(a, b, a);
+#endif
   uint32_t m[NL];
   Fe r;
   uint64_t acc = 0;
@@ -250,6 +455,9 @@ ZK_HD Fe mul(const Fe& a, const Fe& b) {
 // harmless while the true sum is non-negative).  Value: < a b / R + p + d.
 template <class P>
 ZK_HD Fe mul_add(const Fe& a, const Fe& b, const Fe& d) {
+#if ZK_BLOCKS_ON
+  if constexpr (P::ASM && P::BLK) return mul_blk<P, true>(a, b, d);
+#endif
   uint32_t m[NL];
   Fe r;
   uint64_t acc = 0;
@@ -282,6 +490,9 @@ ZK_HD Fe mul_add(const Fe& a, const Fe& b, const Fe& d) {
 // r = a^2 * 2^-261 + d, as mul_add
 template <class P>
 ZK_HD Fe sqr_add(const Fe& a, const Fe& d) {
+#if ZK_BLOCKS_ON
+  if constexpr (P::ASM && P::BLK) return sqr_blk<P, true>(a, d);
+#endif
   uint32_t m[NL], dd[NL];
   Fe r;
 #pragma unroll
@@ -337,6 +548,9 @@ ZK_HD Fe bsubadd(const uint32_t (&c)[NL], const Fe& a, const Fe& b) {
 // squaring: off-diagonal products once, doubled operand
 template <class P>
 ZK_HD Fe sqr(const Fe& a) {
+#if ZK_BLOCKS_ON
+  if constexpr (P::ASM && P::BLK) return sqr_blk<P, false>(a, a);
+#endif
   uint32_t m[NL], d[NL];
   Fe r;
 #pragma unroll
@@ -456,6 +670,9 @@ ZK_HD Fe subk(const Fe& a, const Fe& b) {
 // two products).  a, c: limbs < 2^30; b, d: limbs < 2^29; a*b + c*d < 169 p^2.
 template <class P>
 ZK_HD Fe mul2(const Fe& a, const Fe& b, const Fe& c, const Fe& d) {
+#if ZK_BLOCKS_ON
+  if constexpr (P::ASM && P::BLK) return mul2_blk<P>(a, b, c, d);
+#endif
   uint32_t m[NL];
   Fe r;
   uint64_t acc = 0;
