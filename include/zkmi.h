@@ -928,6 +928,57 @@ int zkmi_note_scan(zkmi_ctx* ctx, const zkmi_note_store* store, const zkmi_mimc*
 int zkmi_ed25519_verify_many(zkmi_ctx* ctx, size_t n, const uint8_t* pubkeys, const uint8_t* sigs, const uint8_t* msgs,
                              const uint64_t* msg_offsets, uint8_t* verdicts);
 
+/* ------------------------------------------------- Transaction authorisation
+ * The whole check the reference's sequencer makes of a transfer or withdrawal
+ * before it touches an account (tx_router.rs:668-793), from the transaction's
+ * fields: the signed message is built on the device,
+ * the human-readable format first and the legacy binary one for those the
+ * first did not verify, and `from` is compared with the signer.  The messages
+ * are tx_router.rs:624-666 byte for byte; the legacy ones are
+ * from || to || amount || nonce || chain_id (88 bytes) and
+ * from || to_l1 || amount || nonce (80 bytes) with little-endian integers,
+ * which for a transfer ASSUMES wincode's layout as DESIGN.md section 2.16
+ * states.  The signature semantics are those of zkmi_ed25519_verify_many. */
+#define ZKMI_TX_TRANSFER    0
+#define ZKMI_TX_WITHDRAWAL  1
+typedef struct {            /* 192 bytes, no implicit padding */
+  uint8_t  from[32];
+  uint8_t  to[32];          /* a transfer's `to`, a withdrawal's to_l1_address */
+  uint64_t amount, nonce, chain_id;   /* chain_id ignored for a withdrawal */
+  uint8_t  signer_pubkey[32];
+  uint8_t  signature[64];
+  uint8_t  kind;            /* ZKMI_TX_* */
+  uint8_t  reserved[7];     /* must be zero */
+} zkmi_signed_tx;
+#ifdef __cplusplus
+static_assert(sizeof(zkmi_signed_tx) == 192, "zkmi_signed_tx is 192 bytes");
+#else
+_Static_assert(sizeof(zkmi_signed_tx) == 192, "zkmi_signed_tx is 192 bytes");
+#endif
+
+#define ZKMI_TXAUTH_OK             0
+#define ZKMI_TXAUTH_BAD_PUBKEY     1   /* signer_pubkey does not decompress */
+#define ZKMI_TXAUTH_FAILED         2   /* neither format verifies (s >= L included) */
+#define ZKMI_TXAUTH_FROM_MISMATCH  3   /* a format verified and from != signer_pubkey */
+#define ZKMI_TXFMT_NONE 0
+#define ZKMI_TXFMT_READABLE 1
+#define ZKMI_TXFMT_LEGACY 2
+/* txs: n records, transfers and withdrawals in any mix; reasons: n bytes, a
+ * ZKMI_TXAUTH_* each; formats: n bytes, the ZKMI_TXFMT_* that verified (NONE
+ * unless the reason is OK or FROM_MISMATCH).  In the order of the reference's
+ * bail!s: the key is judged first; the readable format is tried; the legacy
+ * format is tried only for records whose readable check gave
+ * ZKMI_SIG_MISMATCH (an s >= L fails under both and is not tried again); `from`
+ * is compared with the signer only when a format verified.  n = 0 does nothing
+ * and launches nothing.  ZKMI_EINVAL for a null argument, a kind that is no
+ * ZKMI_TX_*, a reserved byte that is not zero, or more than 2^26 records;
+ * neither output is then written.  The call keeps 540 bytes a record of
+ * workspace on the context (the record 192, its message slot 304, the length,
+ * k, the retry list, two verdicts, reason and format), and shares
+ * zkmi_ed25519_verify_many's tables: 2560 bytes a record for at most 2^18
+ * records at a time, and the table of B. */
+int zkmi_tx_auth_many(zkmi_ctx* ctx, size_t n, const zkmi_signed_tx* txs, uint8_t* reasons, uint8_t* formats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,7 @@ SIGNATURES = [
     ("zkmi_note_scan", ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint32, sz, u8p, u8p, ctypes.c_uint32, ctypes.c_uint32,
                                       u32p, u32p, u32p, u32p, u64p, u8p, u8p, u32p, u8p]),
     ("zkmi_ed25519_verify_many", ctypes.c_int, [vp, sz, u8p, u8p, u8p, u64p, u8p]),
+    ("zkmi_tx_auth_many", ctypes.c_int, [vp, sz, vp, u8p, u8p]),
 ]
 
 

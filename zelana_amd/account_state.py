@@ -119,7 +119,11 @@ class DeviceAccountState:
         place of a tuple.  The signatures of all batches are checked in one
         pass (tx_auth.verify_signed: the readable message first, the legacy
         one for the failures) before anything changes, and a refused one
-        raises ValueError naming the batch, the index and the reason.  The
+        raises ValueError naming the batch, the index and the reason.  With a
+        gpu.Ed25519Verifier that pass takes tx_auth's device path: the entries
+        go to the device as fixed-width records, and the messages are built,
+        verified, retried and `from` compared there (zkmi_tx_auth_many); a
+        verifier with verify_many alone takes the host path.  The
         circuit's `signature` input then carries the first 31 bytes of the
         signature as a big-endian integer (tx_auth.signature_field): a
         pass-through value the circuit does not constrain; the check that

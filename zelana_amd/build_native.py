@@ -25,6 +25,7 @@ FF_PROBE_1MAD = os.path.join(HERE, "libzkmi_ffprobe_1mad.so")  # the same probe,
 FF_HOST = os.path.join(HERE, "libff_host.so")          # the same table on the CPU (tests/native/ff_host_shim.cpp)
 NC_PROBE = os.path.join(HERE, "libzkmi_ncprobe.so")    # note_crypt.h op table on the device (tests/device/), tests only
 ED_PROBE = os.path.join(HERE, "libzkmi_edprobe.so")    # ed25519.h op table on the device (tests/device/), tests only
+TX_PROBE = os.path.join(HERE, "libzkmi_txprobe.so")    # tx_msg.h's message builders on the device (tests/device/), tests only
 ROCM_LIB = "/opt/rocm/lib"
 ARCH = os.environ.get("ZKMI_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -81,6 +82,7 @@ def build(verbose: bool = False) -> str:
     _build_ff_ops(verbose)
     _build_nc_probe(verbose)
     _build_ed_probe(verbose)
+    _build_tx_probe(verbose)
     if verbose:
         print("built", LIB)
     return LIB
@@ -165,6 +167,23 @@ def _build_ed_probe(verbose: bool):
         raise RuntimeError("ed25519 probe build failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
     if verbose:
         print("built", ED_PROBE)
+
+
+def _build_tx_probe(verbose: bool):
+    """libzkmi_txprobe.so: the four message builders of tx_msg.h on the device,
+    one lane a case (tests/device/tx_msg_probe.hip).  It does not link
+    libzkmi.so, and only the tests load it; the same builders run on the CPU as
+    a stand-alone program the tests build themselves (tests/host/tx_msg_check.cpp)."""
+    src = os.path.join(HERE, "..", "tests", "device", "tx_msg_probe.hip")
+    deps = [src, os.path.join(CSRC, "tx_msg.h")]
+    if os.path.exists(TX_PROBE) and all(os.path.getmtime(d) <= os.path.getmtime(TX_PROBE) for d in deps):
+        return
+    cmd = [HIPCC] + HIP_FLAGS + ["-shared", "-L" + ROCM_LIB, "-Wl,-rpath," + ROCM_LIB, "-o", TX_PROBE, src]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("tx_msg probe build failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
+    if verbose:
+        print("built", TX_PROBE)
 
 
 if __name__ == "__main__":

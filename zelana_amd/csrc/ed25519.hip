@@ -17,12 +17,17 @@
 // table of -A (2560 contiguous bytes) lies in the workspace; the curve kernel
 // is launched over at most ED_CHUNK signatures at a time, which bounds that
 // table whatever n is.
+//
+// The curve kernel has a second form for tx_auth.hip: keys
+// and signatures read from zkmi_signed_tx records where they lie, and an
+// optional list of the records to take.  ed_curve_pass launches either.
 #include <string.h>
 
 #include <algorithm>
 
 #include "zkmi_internal.h"
 #include "ed25519.h"
+#include "tx_msg.h"
 
 namespace zk {
 
@@ -82,12 +87,17 @@ struct EdLdsTable {
 
 // signatures [first, first + m); tab: m tables of 640 words.  Two waves a
 // SIMD: the register cap of 256 that goes with it costs 60 bytes of scratch a
-// lane.
+// lane.  TX: pk is n zkmi_signed_tx records, which
+// hold key and signature (sig is not read); lane j of the call takes record
+// idx[first + j], or first + j when idx is null.  k and verdict are indexed by
+// record either way.
+template <bool TX>
 __global__ void __launch_bounds__(ED_CURVE_B, ED_CURVE_WAVES) k_ed_curve(const uint32_t* __restrict__ pk,
                                                          const uint32_t* __restrict__ sig,
                                                          const uint32_t* __restrict__ kk,
                                                          const uint32_t* __restrict__ tab_b, uint4* tab,
-                                                         uint32_t first, uint32_t m, uint8_t* __restrict__ verdict) {
+                                                         const uint32_t* __restrict__ idx, uint32_t first, uint32_t m,
+                                                         uint8_t* __restrict__ verdict) {
   __shared__ EdCached tb_s[ED_TABLE];
   {
     uint32_t* d = reinterpret_cast<uint32_t*>(tb_s);
@@ -96,12 +106,12 @@ __global__ void __launch_bounds__(ED_CURVE_B, ED_CURVE_WAVES) k_ed_curve(const u
   }
   const uint32_t lane = blockIdx.x * ED_CURVE_B + threadIdx.x;
   if (lane >= m) return;
-  const size_t i = (size_t)first + lane;
+  const size_t i = TX && idx ? (size_t)idx[first + lane] : (size_t)first + lane;
+  const uint32_t* a_at = TX ? pk + TX_REC_WORDS * i + TX_REC_SIGNER : pk + 8 * i;
+  const uint32_t* sig_at = TX ? pk + TX_REC_WORDS * i + TX_REC_SIG : sig + 16 * i;
   uint32_t a_bytes[8], r[8], s[8], k[8];
 #pragma unroll
-  for (int w = 0; w < 8; w++) {
-    a_bytes[w] = pk[8 * i + w], r[w] = sig[16 * i + w], s[w] = sig[16 * i + 8 + w], k[w] = kk[8 * i + w];
-  }
+  for (int w = 0; w < 8; w++) a_bytes[w] = a_at[w], r[w] = sig_at[w], s[w] = sig_at[8 + w], k[w] = kk[8 * i + w];
   EdPoint a = ed_identity();
   const bool a_ok = ed_decompress(a, a_bytes), s_ok = sc_is_canonical(s);
   const EdLaneTable tq{tab + (size_t)lane * (ED_TABLE * ED_CACHED_WORDS / 4)};
@@ -127,21 +137,45 @@ static int ed_base_table(zkmi_ctx* ctx, uint32_t** d_tab) {
   return 0;
 }
 
+// The curve kernel over n signatures on the context stream, in chunks of at
+// most ED_CHUNK, timed under `timer`.  rec null: dense keys and signatures,
+// signature i at index i.  rec given: the records of tx_auth.hip, taken by
+// idx[0 .. n) (null: records 0 .. n - 1); pk and sig are not read.
+int ed_curve_pass(zkmi_ctx* ctx, const char* timer, const uint32_t* pk, const uint32_t* sig, const uint32_t* rec,
+                  const uint32_t* idx, const uint32_t* k, size_t n, uint8_t* verdict) {
+  const size_t chunk = std::min(n, ED_CHUNK);
+  uint32_t *d_tab, *d_tab_b;
+  ZK_TRY(ed_base_table(ctx, &d_tab_b));
+  ZK_TRY(ctx->ws.get("ed_table", chunk * sizeof(EdCached) * ED_TABLE, (void**)&d_tab));
+  {
+    ScopedKernelTimer tm(ctx, timer);
+    for (size_t first = 0; first < n; first += chunk) {
+      const size_t m = std::min(chunk, n - first);
+      if (rec)
+        k_ed_curve<true><<<ed_blocks(m, ED_CURVE_B), ED_CURVE_B, 0, ctx->stream>>>(rec, rec, k, d_tab_b, (uint4*)d_tab, idx,
+                                                                                  (uint32_t)first, (uint32_t)m, verdict);
+      else
+        k_ed_curve<false><<<ed_blocks(m, ED_CURVE_B), ED_CURVE_B, 0, ctx->stream>>>(pk, sig, k, d_tab_b, (uint4*)d_tab, nullptr,
+                                                                                   (uint32_t)first, (uint32_t)m, verdict);
+    }
+  }
+  ZK_HIP(hipGetLastError());
+  return 0;
+}
+
 // arguments already checked; n >= 1
 static int ed_verify_many(zkmi_ctx* ctx, size_t n, const uint8_t* pubkeys, const uint8_t* sigs, const uint8_t* msgs,
                           const uint64_t* off, uint8_t* verdicts) {
-  const size_t total = off[n], chunk = std::min(n, ED_CHUNK);
-  uint32_t *d_pk, *d_sig, *d_k, *d_tab, *d_tab_b;
+  const size_t total = off[n];
+  uint32_t *d_pk, *d_sig, *d_k;
   uint64_t* d_off;
   uint8_t *d_msg, *d_verdict;
-  ZK_TRY(ed_base_table(ctx, &d_tab_b));
   ZK_TRY(ctx->ws.get("ed_pk", n * 32, (void**)&d_pk));
   ZK_TRY(ctx->ws.get("ed_sig", n * 64, (void**)&d_sig));
   ZK_TRY(ctx->ws.get("ed_off", (n + 1) * 8, (void**)&d_off));
   ZK_TRY(ctx->ws.get("ed_msg", std::max<size_t>(total, 1), (void**)&d_msg));
   ZK_TRY(ctx->ws.get("ed_k", n * 32, (void**)&d_k));
   ZK_TRY(ctx->ws.get("ed_verdict", n, (void**)&d_verdict));
-  ZK_TRY(ctx->ws.get("ed_table", chunk * sizeof(EdCached) * ED_TABLE, (void**)&d_tab));
   ZK_HIP(hipMemcpyAsync(d_pk, pubkeys, n * 32, hipMemcpyHostToDevice, ctx->stream));
   ZK_HIP(hipMemcpyAsync(d_sig, sigs, n * 64, hipMemcpyHostToDevice, ctx->stream));
   ZK_HIP(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -151,15 +185,7 @@ static int ed_verify_many(zkmi_ctx* ctx, size_t n, const uint8_t* pubkeys, const
     k_ed_hash<<<ed_blocks(n, ED_HASH_B), ED_HASH_B, 0, ctx->stream>>>(d_pk, d_sig, d_msg, d_off, (uint32_t)n, d_k);
   }
   ZK_HIP(hipGetLastError());
-  {
-    ScopedKernelTimer tm(ctx, "ed25519_curve");
-    for (size_t first = 0; first < n; first += chunk) {
-      const size_t m = std::min(chunk, n - first);
-      k_ed_curve<<<ed_blocks(m, ED_CURVE_B), ED_CURVE_B, 0, ctx->stream>>>(d_pk, d_sig, d_k, d_tab_b, (uint4*)d_tab,
-                                                                          (uint32_t)first, (uint32_t)m, d_verdict);
-    }
-  }
-  ZK_HIP(hipGetLastError());
+  ZK_TRY(ed_curve_pass(ctx, "ed25519_curve", d_pk, d_sig, nullptr, nullptr, d_k, n, d_verdict));
   ZK_HIP(hipMemcpyAsync(verdicts, d_verdict, n, hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(hipStreamSynchronize(ctx->stream));
   return timer_flush(ctx);

@@ -242,6 +242,13 @@ int ctx_sync_all(zkmi_ctx* ctx);
 int ctx_pinned_get(zkmi_ctx* ctx, size_t bytes, void** out);
 void ctx_pinned_put(zkmi_ctx* ctx, void* p);
 
+// Ed25519 curve pass (ed25519.hip) over n signatures on the context stream,
+// timed under `timer`: dense keys and signatures (rec null), or the
+// zkmi_signed_tx records of tx_auth.hip taken by idx[0 .. n) (idx null: in
+// order).  k (8 words) and verdict (a byte) are indexed by signature / record.
+int ed_curve_pass(zkmi_ctx* ctx, const char* timer, const uint32_t* pk, const uint32_t* sig, const uint32_t* rec,
+                  const uint32_t* idx, const uint32_t* k, size_t n, uint8_t* verdict);
+
 // MSM entry (msm.hip): device scalars, result canonical affine
 int msm_device(zkmi_ctx* ctx, const zkmi_bases* b, size_t offset, const void* d_scalars, size_t n,
                uint64_t* out_affine);

@@ -1249,6 +1249,14 @@ class NoteStoreDevice(_Handle):
 
 
 SIG_OK, SIG_BAD_PUBKEY, SIG_BAD_S, SIG_MISMATCH = 0, 1, 2, 3  # ZKMI_SIG_*
+TX_TRANSFER, TX_WITHDRAWAL = 0, 1  # ZKMI_TX_*
+TXAUTH_OK, TXAUTH_BAD_PUBKEY, TXAUTH_FAILED, TXAUTH_FROM_MISMATCH = 0, 1, 2, 3  # ZKMI_TXAUTH_*
+TXFMT_NONE, TXFMT_READABLE, TXFMT_LEGACY = 0, 1, 2  # ZKMI_TXFMT_*
+# zkmi_signed_tx, field for field: 192 bytes, no padding
+SIGNED_TX_DTYPE = np.dtype([("from", np.uint8, 32), ("to", np.uint8, 32), ("amount", "<u8"), ("nonce", "<u8"),
+                            ("chain_id", "<u8"), ("signer_pubkey", np.uint8, 32), ("signature", np.uint8, 64),
+                            ("kind", np.uint8), ("reserved", np.uint8, 7)])
+assert SIGNED_TX_DTYPE.itemsize == 192
 
 
 class Ed25519Verifier:
@@ -1289,3 +1297,20 @@ class Ed25519Verifier:
                                              ms.ctypes.data_as(u8p), _p64(off), out.ctypes.data_as(u8p)),
               "zkmi_ed25519_verify_many")
         return out[:n]
+
+    def auth_records(self, records):
+        """The sequencer's whole check of transfers and withdrawals from their
+        fields (zkmi_tx_auth_many): the signed messages are
+        built on the device, the readable format first and the legacy one for
+        those it did not verify, and `from` is compared with the signer.
+        records: a numpy array of SIGNED_TX_DTYPE, transfers and withdrawals
+        in any mix -> (reasons, formats), two uint8 arrays of TXAUTH_* and
+        TXFMT_* codes"""
+        rec = np.ascontiguousarray(records)
+        if rec.dtype != SIGNED_TX_DTYPE or rec.ndim != 1:
+            raise ValueError("auth_records: a one-dimensional array of gpu.SIGNED_TX_DTYPE")
+        n = rec.size
+        reasons, formats = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        check(lib().zkmi_tx_auth_many(self.ctx.h, n, rec.ctypes.data if n else None, reasons.ctypes.data_as(u8p),
+                                      formats.ctypes.data_as(u8p)), "zkmi_tx_auth_many")
+        return reasons[:n], formats[:n]

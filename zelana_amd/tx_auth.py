@@ -10,13 +10,22 @@ order of the reference's `bail!`s:
   VERIFICATION_FAILED        neither message format verifies (s >= L included)
   FROM_MISMATCH              a format verified, and `from` is not signer_pubkey
   OK
-The human-readable message is tried first, for all transactions in one
-verify_many; the legacy binary message is tried in a second verify_many over
-the failures alone.  The messages are built in Python (ed25519.py); building
-them on the device is not part of this."""
+The human-readable message is tried first, for all transactions, and the
+legacy binary message in a second pass over the failures alone.  Two paths
+give the same answer:
+  * the device path (a verifier with auth_records, which gpu.Ed25519Verifier
+    has): pack() turns the transactions into fixed-width records, and the
+    device builds both messages, verifies, retries and compares `from` with
+    the signer (zkmi_tx_auth_many, DESIGN.md §2.17);
+  * the host path (device_messages=False, or a verifier with verify_many
+    alone, such as ModelVerifier): the messages are built in Python
+    (ed25519.py) and go through two verify_many calls.
+A signature of the wrong length is a host matter on both."""
 from __future__ import annotations
 
 from dataclasses import dataclass
+
+import numpy as np
 
 from . import ed25519 as E
 from .r1cs import R
@@ -83,12 +92,59 @@ def signature_field(signature: bytes) -> int:
     return int.from_bytes(bytes(signature)[:31], "big")
 
 
-def _verify(verifier, items):
-    """-> ([reason], [format or None])"""
+def pack(items):
+    """SignedTransfer / SignedWithdrawal each -> the records auth_records takes
+    (gpu.SIGNED_TX_DTYPE, the C ABI's zkmi_signed_tx).  No message is built
+    here.  A signature that is not 64 bytes goes in as zeros."""
+    from .gpu import SIGNED_TX_DTYPE, TX_TRANSFER, TX_WITHDRAWAL
+    items = list(items)
+    n = len(items)
+    kinds = [TX_WITHDRAWAL if isinstance(t, SignedWithdrawal) else TX_TRANSFER for t in items]
+    tos = [t.to_l1_address if k else t.to for t, k in zip(items, kinds)]
+    if any(len(t.from_) != 32 or len(t.signer_pubkey) != 32 or len(to) != 32 for t, to in zip(items, tos)):
+        raise ValueError("32-byte from, to and signer_pubkey")
+    blob = b"".join([b"".join((t.from_, to, t.signer_pubkey, t.signature if len(t.signature) == 64 else bytes(64)))
+                     for t, to in zip(items, tos)])
+    rec = np.zeros(n, SIGNED_TX_DTYPE)
+    cols = np.frombuffer(blob, np.uint8).reshape(n, 160)
+    rec["from"], rec["to"], rec["signer_pubkey"], rec["signature"] = cols[:, :32], cols[:, 32:64], cols[:, 64:96], cols[:, 96:]
+    ints = {"amount": [int(t.amount) for t in items], "nonce": [int(t.nonce) for t in items],
+            "chain_id": [0 if k else int(t.chain_id) for t, k in zip(items, kinds)]}
+    for name, column in ints.items():
+        if n and not (0 <= min(column) and max(column) < E.U64):
+            raise ValueError("u64 amount, nonce and chain_id")
+        rec[name] = np.array(column, np.uint64)
+    rec["kind"] = kinds
+    return rec
+
+
+_REASONS = (OK, INVALID_PUBKEY, VERIFICATION_FAILED, FROM_MISMATCH)  # gpu.TXAUTH_*
+_FORMATS = (None, READABLE, LEGACY)                                   # gpu.TXFMT_*
+
+
+def _verify_on_device(verifier, items):
+    r, f = verifier.auth_records(pack(items))
+    reasons, formats = [_REASONS[v] for v in r.tolist()], [_FORMATS[v] for v in f.tolist()]
+    for i in [i for i, t in enumerate(items) if len(t.signature) != 64]:
+        if reasons[i] != INVALID_PUBKEY:
+            reasons[i], formats[i] = INVALID_SIGNATURE_LENGTH, None
+    return reasons, formats
+
+
+def _verify(verifier, items, device_messages=None):
+    """-> ([reason], [format or None]).  device_messages: None takes the device
+    path when the verifier has auth_records, False the host path, True the
+    device path or a ValueError."""
     items = list(items)
     n = len(items)
     if n == 0:
         return [], []
+    if device_messages is None:
+        device_messages = hasattr(verifier, "auth_records")
+    if device_messages:
+        if not hasattr(verifier, "auth_records"):
+            raise ValueError("device_messages=True needs a verifier with auth_records")
+        return _verify_on_device(verifier, items)  # pack() checks the lengths
     if any(len(bytes(t.signer_pubkey)) != 32 or len(bytes(t.from_)) != 32 for t in items):
         raise ValueError("32-byte signer_pubkey and from")
     msgs = [t.messages() for t in items]
@@ -119,20 +175,23 @@ def _verify(verifier, items):
     return reasons, formats
 
 
-def verify_signed(verifier, items):
+def verify_signed(verifier, items, device_messages: bool | None = None):
     """transfers and withdrawals mixed, in one pass -> ([reason], [format])"""
-    return _verify(verifier, items)
+    return _verify(verifier, items, device_messages)
 
 
-def verify_transfers(verifier, txs):
+def verify_transfers(verifier, txs, device_messages: bool | None = None):
     """txs: SignedTransfer each -> ([reason], [READABLE / LEGACY / None]);
-    verifier: anything with verify_many(pubkeys, msgs, sigs) -> SIG_* codes"""
-    return _verify(verifier, txs)
+    verifier: anything with verify_many(pubkeys, msgs, sigs) -> SIG_* codes,
+    or with auth_records as well (gpu.Ed25519Verifier).  device_messages: None
+    builds the messages on the device when the verifier has auth_records,
+    False builds them in Python; the result is the same."""
+    return _verify(verifier, txs, device_messages)
 
 
-def verify_withdrawals(verifier, reqs):
+def verify_withdrawals(verifier, reqs, device_messages: bool | None = None):
     """reqs: SignedWithdrawal each -> ([reason], [READABLE / LEGACY / None])"""
-    return _verify(verifier, reqs)
+    return _verify(verifier, reqs, device_messages)
 
 
 class ModelVerifier:
